@@ -8,8 +8,14 @@ pass of the hot path over the batch: compute_states followed by compute_adjoints
 batch * N fused RK4 state+costate steps.  Inputs are synthetic and already resident in HBM.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, pre-warms, runs the W warm-up steps, times the K steps and prints the headline line; with
+--dump-outputs DIR it also writes the outputs of the last timed step as DIR/<name>.npy (see dump_outputs).  --full adds
+everything else this script measures: the PMC traffic collected in child processes, the per-kernel HIP-event timings and
+roofline of the headline kernels, the secondary legs and the CPU baseline with its parity check.
 
 Multi-GPU: the batch axis shards with no data-path exchange; the only collective is the all-reduce(SUM) of the
 objective sum over ranks (north_star), 8 bytes per step, issued asynchronously so that it overlaps the next step's
@@ -626,6 +632,25 @@ def bl5_metric(ocs, dev, batch=8192, nsteps=4000, reps=2, shard=True):
             "finite": bool(torch.isfinite(lam[0]).all().item()) and bool(torch.isfinite(J).all().item())}
 
 
+DUMP_TRAJECTORIES = 256      # trajectories of x / lam / dJdu written by --dump-outputs (~25 MB at N = 1000, nS = 4)
+DUMP_J_MAX = 1 << 20         # entries of J written by --dump-outputs (all of them up to this batch)
+
+
+def dump_outputs(out_dir, x, J, lam, dJdu):
+    """Writes what the headline pass pair hands its caller -- x [N+1][nS+1][B], J [B], lam [N+1][nS+1][B],
+    dJdu [2N+1][nC][B] -- as out_dir/<name>.npy in float64.  x, lam and dJdu are written for a fixed, seeded sample of
+    DUMP_TRAJECTORIES trajectories (sorted batch indices, the same for every run with the same --batch), J for a sample
+    of up to DUMP_J_MAX trajectories (the whole batch below that), so the files stay well under 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    batch = J.shape[0]
+    rng = np.random.default_rng(20260416)
+    cols = torch.tensor(np.sort(rng.choice(batch, min(batch, DUMP_TRAJECTORIES), replace=False)), device=J.device)
+    jcols = torch.tensor(np.sort(rng.choice(batch, min(batch, DUMP_J_MAX), replace=False)), device=J.device)
+    for name, t in (("x", x.index_select(2, cols)), ("J", J.index_select(0, jcols)),
+                    ("lam", lam.index_select(2, cols)), ("dJdu", dJdu.index_select(2, cols))):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -638,12 +663,21 @@ def main():
     ap.add_argument("--prewarm", type=float, default=1.0,
                     help="seconds of untimed passes before the W warm-up steps: the clocks of an idle GPU take a few "
                          "hundred ms to come up, and the K timed steps last only a few ms")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write x, J, lam and dJdu of the last timed step (a fixed, seeded sample of trajectories) as "
+                         "DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: live PMC traffic, per-kernel event timings and "
+                         "roofline, the secondary legs, the CPU baseline and its parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not collect the PMC traffic counters in child processes first (roofline.traffic is then the "
-                         "figure replayed from profiles/)")
-    ap.add_argument("--no-fb-sweep", action="store_true", help="skip the secondary legs (fb_sweep, BL-4, BL-5, large batch)")
+                    help="with --full: do not collect the PMC traffic counters in child processes first (roofline.traffic "
+                         "is then the figure replayed from profiles/)")
+    ap.add_argument("--no-fb-sweep", action="store_true",
+                    help="with --full: skip the secondary legs (fb_sweep, BL-4, BL-5, large batch)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -651,7 +685,8 @@ def main():
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} needs torch.distributed.run with --nproc-per-node {args.gpus}")
     import torch.distributed as dist
-    LIVE = live_traffic() if (world == 1 and not args.no_live_traffic and "RANK" not in os.environ) else None
+    LIVE = (live_traffic() if (args.full and world == 1 and not args.no_live_traffic and "RANK" not in os.environ)
+            else None)
     # OCS_FORCE_COLLECTIVES=1 under torch.distributed.run with ONE process: the process group is created and every
     # collective of the N-rank path (asynchronous objective all-reduce and its drain, barriers, max over ranks, the
     # gathers of the secondary legs) executes on RCCL with world size 1 -- the rehearsal a one-GPU box allows
@@ -694,7 +729,7 @@ def main():
     Jsums = torch.zeros((max(args.steps, args.warmup, 1), 1), dtype=torch.float64, device=dev)
     pending = []
 
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)] if args.full else []
 
     def one_step(i, k=None):
         if k is not None:
@@ -738,47 +773,24 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # per-kernel durations (roofline): K more steps, untimed, with HIP events between the two kernels (an event record between
-    # kernels costs a few us of GPU idle time, so the timed steps above carry none, and these come after them)
-    for k in range(args.steps):
-        one_step(k, k)
-    drain()
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x, J, lam, dJdu)
+    if args.full:
+        # per-kernel durations (roofline): K more steps, untimed, with HIP events between the two kernels (an event record
+        # between kernels costs a few us of GPU idle time, so the timed steps above carry none, and these come after them)
+        for k in range(args.steps):
+            one_step(k, k)
+        drain()
+        torch.cuda.synchronize()
     if use_dist:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-
-    # per-kernel durations from HIP events on the launch stream (torch's current stream)
-    t_fwd = float(np.mean([e[0].elapsed_time(e[1]) for e in ev])) * 1e-3
-    t_bwd = float(np.mean([e[1].elapsed_time(e[2]) for e in ev])) * 1e-3
-    ev_f = sorted(e[0].elapsed_time(e[1]) * 1e3 for e in ev)
-    ev_b = sorted(e[1].elapsed_time(e[2]) * 1e3 for e in ev)
-    nA = NS + 1
-    bytes_fwd = 8 * (nA + 2 * NC) * batch * NSTEPS           # write x, read u (2 new samples/step)
-    bytes_bwd = 8 * (2 * nA + 4 * NC) * batch * NSTEPS       # read x, write lam, read u, write dJdu
     ok = bool(torch.isfinite(J).all().item()) and bool(torch.isfinite(dJdu).all().item())
 
     line = None
     if rank == 0:
         steps_total = total_batch * NSTEPS * args.steps
-        # HBM bytes per launch of the dominant kernel from rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE, separate
-        # passes, calibrated as MI355X_MICROARCH.md prescribes); NOT measured by this run: replayed from the named
-        # profile of the same kernels, or null
-        traffic, traffic_source = None, None
-        tr_path = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tr_path):
-            try:
-                tr = json.load(open(tr_path))
-                if tr.get("batch") == batch and tr.get("kernel") == "k_backward":
-                    traffic = tr.get("hbm_bytes_per_launch")
-                    traffic_source = (f"{tr.get('source')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of these kernels; "
-                                      "replayed from that file, not collected by this run)")
-            except Exception:
-                traffic = None
-        if LIVE and "bwd_one_set" in LIVE and batch == BATCH:
-            traffic = LIVE["bwd_one_set"]["hbm_bytes_per_launch"]
-            traffic_source = LIVE["source"]
         line = {
             "metric": "RK4 state+costate steps/sec (batch*nSteps)",
             "value": steps_total / dt,
@@ -801,6 +813,35 @@ def main():
                        "batch_per_gpu": batch, "batch_total": total_batch, "parallelism": f"batch-sharded x{world}",
                        "mapping": "automatic: compute_states k_forward_p2 (wave-specialised, minimal recursion wave), "
                                   "compute_adjoints k_backward_scan (scan over time)"},
+            "finite": ok,
+        }
+    if rank == 0 and args.full:
+        # per-kernel durations from HIP events on the launch stream (torch's current stream)
+        t_fwd = float(np.mean([e[0].elapsed_time(e[1]) for e in ev])) * 1e-3
+        t_bwd = float(np.mean([e[1].elapsed_time(e[2]) for e in ev])) * 1e-3
+        ev_f = sorted(e[0].elapsed_time(e[1]) * 1e3 for e in ev)
+        ev_b = sorted(e[1].elapsed_time(e[2]) * 1e3 for e in ev)
+        nA = NS + 1
+        bytes_fwd = 8 * (nA + 2 * NC) * batch * NSTEPS           # write x, read u (2 new samples/step)
+        bytes_bwd = 8 * (2 * nA + 4 * NC) * batch * NSTEPS       # read x, write lam, read u, write dJdu
+        # HBM bytes per launch of the dominant kernel from rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE, separate
+        # passes, calibrated on a copy of known size); NOT measured by this run: replayed from the named
+        # profile of the same kernels, or null
+        traffic, traffic_source = None, None
+        tr_path = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tr_path):
+            try:
+                tr = json.load(open(tr_path))
+                if tr.get("batch") == batch and tr.get("kernel") == "k_backward":
+                    traffic = tr.get("hbm_bytes_per_launch")
+                    traffic_source = (f"{tr.get('source')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of these kernels; "
+                                      "replayed from that file, not collected by this run)")
+            except Exception:
+                traffic = None
+        if LIVE and "bwd_one_set" in LIVE and batch == BATCH:
+            traffic = LIVE["bwd_one_set"]["hbm_bytes_per_launch"]
+            traffic_source = LIVE["source"]
+        line.update({
             "roofline": {"bound": "hbm", "kernel": "k_backward_scan (compute_adjoints + compute_dJdu)",
                          "achieved": bytes_bwd / t_bwd / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": bytes_bwd / t_bwd / 1e9 / HBM_PEAK_GBPS, "traffic": traffic,
@@ -816,12 +857,11 @@ def main():
                         # the pass pair over the timed (event-free) steps of this rank
                         "pass_pair_GBps": (bytes_fwd + bytes_bwd) * args.steps / dt / 1e9,
                         "pass_pair_frac": (bytes_fwd + bytes_bwd) * args.steps / dt / 1e9 / HBM_PEAK_GBPS},
-            "finite": ok,
-        }
+        })
         if LIVE:
             line["traffic_collected_by_this_run"] = LIVE
     # secondary legs: every rank runs them on its shard (collectives inside)
-    if not args.no_fb_sweep:
+    if args.full and not args.no_fb_sweep:
         fb = fb_sweep_metric(ocs, dev)
         b4 = bl4_metric(ocs, dev)
         b5 = bl5_metric(ocs, dev)
@@ -848,7 +888,7 @@ def main():
             if ssr:
                 line["other_configs"]["strong-scaling readiness (8-GPU shard sizes on one GPU)"] = ssr
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb, ref = cpu_baseline(tspan, x0_h, u_h)
             line["cpu_baseline"] = cb
             # the baseline run doubles as a parity check of the timed buffers

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/r04e
 mkdir -p $OUT
 cd $ROOT
 timeout -k 10 900 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -12 $OUT/pytest_gpu.log
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || tail -20 $OUT/bench.err
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || tail -20 $OUT/bench.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r04e/bench.json"))

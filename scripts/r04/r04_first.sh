@@ -8,8 +8,8 @@ mkdir -p $OUT
 cd $ROOT
 timeout -k 10 400 python -m pytest tests/test_gpu_fb_sweep.py -m gpu -x -q > $OUT/pytest_fbs.log 2>&1 || { tail -30 $OUT/pytest_fbs.log; exit 1; }
 tail -3 $OUT/pytest_fbs.log
-timeout -k 10 300 python bench.py > $OUT/bench1.json 2> $OUT/bench1.err || { tail -20 $OUT/bench1.err; exit 1; }
-timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench2.json 2> $OUT/bench2.err || { tail -20 $OUT/bench2.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $OUT/bench1.json 2> $OUT/bench1.err || { tail -20 $OUT/bench1.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench2.json 2> $OUT/bench2.err || { tail -20 $OUT/bench2.err; exit 1; }
 for d in 1 2 3; do echo "depth $d"; OCS_FBS_DEPTH=$d timeout -k 10 120 python scripts/fbs_time.py; done > $OUT/fbs_depth.log 2>&1
 cat $OUT/fbs_depth.log
 for r in 1 3; do ROTATE=$r timeout -k 10 120 python scripts/pair_rotate.py; done > $OUT/rotate.log 2>&1

@@ -7,8 +7,8 @@ OUT=$ROOT/gpurun_out/r04l
 mkdir -p $OUT
 cd $ROOT
 timeout -k 10 600 python -m pytest tests/test_gpu_multi_device.py tests/test_gpu_fb_sweep.py -m gpu -q > $OUT/pytest.log 2>&1; echo "pytest rc $?"; tail -4 $OUT/pytest.log
-OCS_FORCE_COLLECTIVES=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_forced.json 2> $OUT/bench_forced.err || tail -20 $OUT/bench_forced.err
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || tail -20 $OUT/bench.err
+OCS_FORCE_COLLECTIVES=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_forced.json 2> $OUT/bench_forced.err || tail -20 $OUT/bench_forced.err
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || tail -20 $OUT/bench.err
 python - <<'PY'
 import json
 for n in ("bench_forced", "bench"):
