@@ -278,9 +278,7 @@ typedef struct ocs_fbs_options {
                            pass (which reads the costate of the sweep before) and the convergence test inside the costate
                            pass; 1 keeps all of them separate kernels, 2 only the midpoints, 3 only the control update
                            of sweeps >= 2 (same results to round-off) */
-  int nWINDOWS;         /* build option, default 0 = automatic (currently 1): with the fused update the batch can be cut
-                           into this many windows that run their sweep loops on separate streams (marching kernels of
-                           one window under the streaming kernels of another); results do not depend on it */
+  int nWINDOWS;         /* ignored, kept for the layout of the struct (results never depended on it) */
   int cost_row;         /* default 0: the running-objective row of xaug (row nS) is left unspecified -- soln of the
                            reference holds x, lam, u and the scalar J only (fb_sweep.m:117-125); 1 writes it */
   double uRelax;        /* extension, default 0 = off: the reference has no damping (u = uNew, :85) and its sweep may
@@ -312,7 +310,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double *x
 /* Diagnostic: the sweep loop the last ocs_fb_sweep(_dev) on this integrator ran --
  * 0 none yet; 1 the reference's sequence kernel by kernel (state pass, pchip midpoints, costate pass, ControlChar on the
  * error points / the grid, convergence bookkeeping, one host round trip per sweep); 2 the same with the control update
- * fused into one kernel and sweeps enqueued one ahead; 3 windows of the batch on their own streams; 4 the two-kernel
+ * fused into one kernel and sweeps enqueued one ahead; 4 the two-kernel
  * sweep (state pass with the control update folded in + costate pass with the convergence test, csrc/ocs_fold_kernel.hpp):
  * registry problems of the logistic family and hipRTC problems created with flag bit 2 (row functions, ocs_ControlChar of
  * the costate alone); 5 the sequence of 1 with the error points off the grid nodes (or a given u0), its kernels gated and

@@ -12,8 +12,8 @@ function soln = gpu_fb_sweep(prob, x0, tspan, options)                         %
          if isfield(options, names{k}), o.(names{k}) = options.(names{k}); end
       end
    end
-   % (the other fields are build options and keep their defaults: fused_update_off, nWINDOWS, cost_row -- the last
-   %  only matters to callers of ocs_fb_sweep_dev that want the running objective at every node)
+   % (the other fields are build options and keep their defaults: fused_update_off, cost_row -- the last only
+   %  matters to callers of ocs_fb_sweep_dev that want the running objective at every node; nWINDOWS is ignored)
    N = numel(tspan) - 1;  nS = numel(x0);  nC = size(prob.ControlBounds, 1);
    x = zeros(nS, N+1);  lam = x;  uI = zeros(nC, o.nINTERP_PTS);  J = 0;  sweeps = int32(0);
    [rc, ~, ~, ~, ~, ~, ~, x, lam, uI, J, sweeps] = calllib('libocs', 'ocs_fb_sweep', integ.hnd.Value, ...

@@ -23,11 +23,9 @@ struct ocs_fbs_state {
   DevBuf QSE;   // error points by interval: offsets [n] (they are sorted: linspace)
   unsigned long long tu_version = 0;
   const ocs_problem_s* tu_prob = nullptr;
-  // windows of the batch on their own streams (fb_sweep with the fused control update)
-  std::vector<hipStream_t> wstreams;
-  std::vector<hipEvent_t> wevents;  // two per window: "sweep done" (ping-pong)
-  hipEvent_t fork = nullptr, stag = nullptr;
-  int* h_nact = nullptr;            // pinned: [windows][nSWEEPS] instances still active after each sweep
+  // sweeps enqueued ahead (fb_sweep paths 2, 4, 5)
+  std::vector<hipEvent_t> wevents;  // "sweep done", one per sweep in flight (ring)
+  int* h_nact = nullptr;            // pinned: [nSWEEPS] instances still active after each sweep
   int h_nact_cap = 0;
   DevBuf nact_slots;                // device: the same counters
   // work arrays
@@ -42,10 +40,7 @@ void ocs_fbs_state_free(ocs_fbs_state* s) {
                     &s->usel, &s->status, &s->maxchange, &s->nactive, &s->x0, &s->stage, &s->metric, &s->anyvalid, &s->dump};
   for (DevBuf* b : bufs) b->release();
   s->nact_slots.release();
-  for (hipStream_t st : s->wstreams) (void)hipStreamDestroy(st);
   for (hipEvent_t e : s->wevents) (void)hipEventDestroy(e);
-  if (s->fork) (void)hipEventDestroy(s->fork);
-  if (s->stag) (void)hipEventDestroy(s->stag);
   if (s->h_nact) (void)hipHostFree(s->h_nact);
   delete s;
 }
@@ -422,7 +417,7 @@ int ocs_compute_x_lam_dev(ocs_integrator g, ocs_problem p, int batch, const doub
   LAUNCH_TRY(launch_forward(describe(p), describe(g), batch, x0, ugrid, xaug, Jd, FwdOpts(), s));
   const FbsTables tb = tabs(g);
   if (costate_forms_midpoints(describe(p), N, batch)) {  // pchip midpoints of x inside the costate kernel
-    LAUNCH_TRY(launch_costate(describe(p), describe(g), batch, xaug, nAug, nullptr, ugrid, nullptr, 0, lam, s, 0, tb.PR));
+    LAUNCH_TRY(launch_costate(describe(p), describe(g), batch, xaug, nAug, nullptr, ugrid, nullptr, 0, lam, s, tb.PR));
     return OCS_OK;
   }
   LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s));
@@ -511,7 +506,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   // (registry problems: where the wave-specialised costate kernels and the gated state pass apply; hipRTC problems: row
   //  functions whose ocs_ControlChar reads the costate alone, fold_supported)
   const bool userfold = p->user != nullptr && fold_supported(pd, gd, batch);
-  const bool fold = fusedup && om == 1.0 && opt->nWINDOWS <= 1 && opt->fused_update_off == 0 &&
+  const bool fold = fusedup && om == 1.0 && opt->fused_update_off == 0 &&
                     (userfold || (costate_forms_midpoints(pd, N, batch) && forward_gate_supported(pd, gd, batch) &&
                                   fold_supported(pd, gd, batch)));
   if (u0grid) {  // u = u0  :76
@@ -525,94 +520,6 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   const int* usel = (const int*)f->usel.p;  // selects the old / new buffer of the ERROR-POINT samples only
   int nactive = batch;
   f->last_path = 1;
-  // ---- fused update, several windows of the batch on their own streams -----------------------------------------
-  // The two marching kernels of a sweep (forward, costate) are latency-bound and leave most of the GPU idle; the
-  // streaming kernels (pchip, control update) are HBM-bound.  Independent windows of the batch, each running its own
-  // sweep loop on its own stream and started one forward pass apart, let one window's marching kernels run under
-  // another's streaming kernels.  Each window stops on its own count of active instances.
-  int nwin = 1;
-  if (fusedup) {
-    // Automatic = 1 for now: measured at batch 16384, 4 windows are host-bound (8 runtime calls per window and sweep,
-    // ~190 us, against ~290 us of GPU time per round) and slower than one stream; a captured graph per window is
-    // the missing piece.  At batch 65536 windows neither gain nor lose (the streaming kernels dominate).
-    nwin = opt->nWINDOWS > 0 ? opt->nWINDOWS : 1;
-    while (nwin > 1 && (batch + nwin - 1) / nwin < 64) --nwin;
-  }
-  if (fusedup && nwin > 1) {
-    f->last_path = 3;
-    const int W = (((batch + nwin - 1) / nwin + 63) / 64) * 64;  // whole tiles of the pipeline kernels
-    nwin = (batch + W - 1) / W;
-    const int nsw = opt->nSWEEPS;
-    while ((int)f->wstreams.size() < nwin) {
-      hipStream_t st;
-      HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      f->wstreams.push_back(st);
-      for (int e = 0; e < 2; ++e) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        f->wevents.push_back(ev);
-      }
-    }
-    if (!f->fork) HIP_TRY(hipEventCreateWithFlags(&f->fork, hipEventDisableTiming));
-    if (!f->stag) HIP_TRY(hipEventCreateWithFlags(&f->stag, hipEventDisableTiming));
-    if (f->h_nact_cap < nwin * nsw) {
-      if (f->h_nact) (void)hipHostFree(f->h_nact);
-      f->h_nact = nullptr;
-      HIP_TRY(hipHostMalloc((void**)&f->h_nact, sizeof(int) * (size_t)nwin * nsw));
-      f->h_nact_cap = nwin * nsw;
-    }
-    OCS_TRY(f->nact_slots.ensure(sizeof(int) * (size_t)nwin * nsw));
-    HIP_TRY(hipMemsetAsync(f->nact_slots.p, 0, sizeof(int) * (size_t)nwin * nsw, s));
-    HIP_TRY(hipEventRecord(f->fork, s));
-    std::vector<int> done(nwin, 0), last(nwin, 0), act(nwin, 0);  // done: finished; last: sweeps enqueued
-    int* dslots = (int*)f->nact_slots.p;
-    auto enqueue = [&](int j, int sweep) -> int {
-      const int off = j * W, cnt = std::min(W, batch - off);
-      hipStream_t st = f->wstreams[j];
-      ProblemDesc pj = pd;
-      if (pj.pb) pj.pb += off;
-      FwdOpts fo;
-      fo.frozen = status + off;
-      fo.dump = f->dump.d() + off;
-      fo.ld = batch;
-      fo.no_cost_row = opt->cost_row == 0;
-      LAUNCH_TRY(launch_forward(pj, gd, cnt, x0 + off, f->ugrid.d() + off, xaug + off, J + off, fo, st));
-      if (sweep == 1 && j + 1 < nwin) HIP_TRY(hipEventRecord(f->stag, st));  // the next window starts one pass later
-      LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, cnt, xaug + off, f->xmid.d() + off, st, batch));
-      LAUNCH_TRY(launch_costate(pj, gd, cnt, xaug + off, nAug, f->xmid.d() + off, f->ugrid.d() + off, status + off,
-                                f->dump.d() + off, lam + off, st, batch));
-      LAUNCH_TRY(launch_control_grid(pj, gd, tb, cnt, xaug + off, nAug, f->xmid.d() + off, lam + off, f->ugrid.d() + off,
-                                     status + off, f->metric.d() + off, opt->uRelTol, opt->uAbsTol, st, batch, nullptr, om));
-      int* slot = dslots + (size_t)j * nsw + (sweep - 1);
-      LAUNCH_TRY(launch_fbs_advance(cnt, sweep, nparts, f->metric.d() + off, (int*)f->anyvalid.p + off,
-                                    (int*)f->usel.p + off, status + off, mc + off, slot, st, batch));
-      HIP_TRY(hipMemcpyAsync(f->h_nact + (size_t)j * nsw + (sweep - 1), slot, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipEventRecord(f->wevents[2 * j + (sweep & 1)], st));
-      return OCS_OK;
-    };
-    for (int j = 0; j < nwin; ++j) {  // sweep 1, staggered
-      HIP_TRY(hipStreamWaitEvent(f->wstreams[j], f->fork, 0));
-      if (j > 0) HIP_TRY(hipStreamWaitEvent(f->wstreams[j], f->stag, 0));
-      OCS_TRY(enqueue(j, 1));
-      last[j] = 1;
-    }
-    for (int live = nwin; live > 0;) {  // round robin: a window gets its next sweep when the previous one is back
-      for (int j = 0; j < nwin; ++j) {
-        if (done[j]) continue;
-        HIP_TRY(hipEventSynchronize(f->wevents[2 * j + (last[j] & 1)]));
-        act[j] = f->h_nact[(size_t)j * nsw + (last[j] - 1)];
-        if (act[j] == 0 || last[j] >= nsw) {
-          done[j] = 1;
-          --live;
-          continue;
-        }
-        ++last[j];
-        OCS_TRY(enqueue(j, last[j]));
-      }
-    }
-    nactive = 0;
-    for (int j = 0; j < nwin; ++j) nactive += act[j];
-  }
   // ---- fused update, one stream, sweeps enqueued one ahead --------------------------------------------------------
   // The host learns the number of active instances of sweep k only after a round trip; waiting for it before
   // enqueuing sweep k+1 left the GPU idle for ~25 us per sweep.  Here sweep k+1 is enqueued first and its kernels
@@ -625,8 +532,8 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   // ... and the same for error points OFF the grid nodes (the reference's default of 1001 points on any grid but N = 1000, a given
   // u0): the kernels of the kernel-by-kernel sequence below, gated and enqueued ahead (path 5).  That sequence waited for the
   // host once per sweep: 485 against ~250 us per sweep at 500 steps.
-  const bool ahead1 = !fusedup && fuo == 0 && opt->nWINDOWS <= 1 && forward_gate_any(pd);
-  if ((fusedup && nwin == 1 && (fold || forward_gate_any(pd))) || ahead1) {
+  const bool ahead1 = !fusedup && fuo == 0 && forward_gate_any(pd);
+  if ((fusedup && (fold || forward_gate_any(pd))) || ahead1) {
     const int nsw = opt->nSWEEPS;
     const bool ownx = fuo == 0 && costate_forms_midpoints(pd, N, batch);   // midpoints inside the costate / control kernels
     f->last_path = fold ? 4 : (fusedup ? 2 : 5);
@@ -679,8 +586,8 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
       fo.gate = gate;
       LAUNCH_TRY(launch_forward(pd, gd, batch, x0, f->ugrid.d(), xaug, J, fo, s));
       const double* xmid = ownx ? nullptr : f->xmid.d();
-      if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s, 0, gate));
-      LAUNCH_TRY(launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, 0, tb.PR,
+      if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s, gate));
+      LAUNCH_TRY(launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, tb.PR,
                                 gate));
       if (!fusedup) {   // error points off the nodes: uNew there with check_convergence (:96, :99-115), then u = uNew on the grid
         if (cps)
@@ -691,18 +598,18 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
                                         f->uerr.d(), usel, (long long)uerrN, f->metric.d(), (int*)f->anyvalid.p, opt->uRelTol,
                                         opt->uAbsTol, s, om, gate));
         LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
-                                      mc, dslots + (sweep - 1), s, 0, gate));
+                                      mc, dslots + (sweep - 1), s, gate));
         // (only the instances that continue take uNew: status is the one k_fbs_advance just wrote, :85 / :82)
-        LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, nullptr, 0.0, 0.0, s, 0,
-                                       gate, om));
+        LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, nullptr, 0.0, 0.0, s, gate,
+                                       om));
         HIP_TRY(hipMemcpyAsync(f->h_nact + (sweep - 1), dslots + (sweep - 1), sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipEventRecord(f->wevents[sweep % nev], s));
         return OCS_OK;
       }
       LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, f->metric.d(),
-                                     opt->uRelTol, opt->uAbsTol, s, 0, gate, om));
+                                     opt->uRelTol, opt->uAbsTol, s, gate, om));
       LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
-                                    mc, dslots + (sweep - 1), s, 0, gate));
+                                    mc, dslots + (sweep - 1), s, gate));
       HIP_TRY(hipMemcpyAsync(f->h_nact + (sweep - 1), dslots + (sweep - 1), sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipEventRecord(f->wevents[sweep % nev], s));
       return OCS_OK;
@@ -716,7 +623,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
     }
     spec_done = true;
   }
-  for (int sweep = 1; !spec_done && !(fusedup && nwin > 1) && sweep <= opt->nSWEEPS && nactive > 0; ++sweep) {  // :79
+  for (int sweep = 1; !spec_done && sweep <= opt->nSWEEPS && nactive > 0; ++sweep) {  // :79
     // uNew = sweep(u): compute_x_lam (:95) ...
     // instances that converged in an earlier sweep are integrated along but store nothing: their x, lam, J stay
     // those of the sweep they converged in (final_sweep(u), :82)
@@ -734,9 +641,9 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
       // costate (:95); uNew = ControlChar(t, x(t), lam(t)) on the grid, in place (:96, :85), with the weighted change at
       // the nodes (:107) folded in.  A just-converged instance takes uNew as well, but it is frozen from now on: its
       // x, lam, J are the ones computed above from the old control, which is what final_sweep(u) returns (:82).
-      LAUNCH_TRY(launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, 0, tb.PR));
+      LAUNCH_TRY(launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, tb.PR));
       LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, f->metric.d(),
-                                     opt->uRelTol, opt->uAbsTol, s, 0, nullptr, om));
+                                     opt->uRelTol, opt->uAbsTol, s, nullptr, om));
       LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
                                     mc, (int*)f->nactive.p, s));
       HIP_TRY(hipMemcpyAsync(&nactive, f->nactive.p, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -759,7 +666,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
     // keeps its OLD control, which is what final_sweep(u) integrates (:82)
     // (lam's pchip midpoints are formed inside the kernel)
     LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, f->xmid.d(), lam, f->ugrid.d(), status, nullptr, 0.0, 0.0,
-                                   s, 0, nullptr, om));
+                                   s, nullptr, om));
     HIP_TRY(hipMemcpyAsync(&nactive, f->nactive.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }

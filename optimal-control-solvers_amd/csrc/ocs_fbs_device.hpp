@@ -233,12 +233,12 @@ __device__ static inline void pchip_mid_run(const PchipTab& T, const double* V, 
 // blockIdx.y = run of kPchipRun intervals
 __global__ __launch_bounds__(256) void k_pchip_mid(PchipTab T, int nrows, int ld, int batch,
                                                    const double* __restrict__ TM, const double* __restrict__ V,
-                                                   double* __restrict__ out, int ldb, const int* __restrict__ gate) {
+                                                   double* __restrict__ out, const int* __restrict__ gate) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   const int i0 = blockIdx.y * kPchipRun;
   if (gate && *gate == 0) return;
   if (b >= batch || i0 >= T.n - 1) return;
-  const size_t B = (size_t)(ldb ? ldb : batch);  // row distance (a window of a larger batch) / trajectories here
+  const size_t B = (size_t)batch;
   for (int r = 0; r < nrows; ++r) {
     double mid[kPchipRun];
     pchip_mid_run<kPchipRun>(T, V + (size_t)r * B + b, (size_t)ld * B, i0, TM, mid);
@@ -265,7 +265,6 @@ struct CostateArgs {
   const int* frozen;   // optional [B]: instances with frozen[b] != 0 (converged in an earlier sweep) store nothing
   double* dump;        // [B] scratch for their stores
   double* lam;         // [N+1][nS][B]
-  int ld;              // row distance when the launch covers a window of a larger batch; 0 = batch
   const int* gate = nullptr;   // optional: the launch does nothing if *gate == 0
 };
 
@@ -276,7 +275,7 @@ __global__ __launch_bounds__(64) void k_costate(const CostateArgs a) {
   using Rec = StepRec<NTC>;
   const int b0 = blockIdx.x * 64 + threadIdx.x;
   const int b = b0 < a.batch ? b0 : a.batch - 1;
-  const size_t B = (size_t)(a.ld ? a.ld : a.batch);
+  const size_t B = (size_t)a.batch;
   const int N = a.N;
   const uniform_ptr PS = as_uniform(a.ps);
   const typename P::Par p = P::load(ParamSrc{PS, a.pb, a.pmask, B, b});
@@ -446,7 +445,6 @@ struct ControlGridArgs {
   // then on it is frozen (its x, lam, J are the ones already computed from the old control, fb_sweep.m:82).
   double* metric;
   double relTol, absTol;
-  int ld;  // row distance when the launch covers a window of a larger batch; 0 = batch
   const int* gate;  // optional: the launch does nothing if *gate == 0
   double relax;     // the samples become u + relax (uNew - u) (1: the reference's u = uNew, fb_sweep.m:85)
 };
@@ -574,7 +572,7 @@ __global__ __launch_bounds__(256) void k_control_grid(const ControlGridArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   const int i0 = blockIdx.y * R;  // first interval of this thread's run
   if (b >= a.batch || a.status[b] != 0) return;
-  const size_t B = (size_t)(a.ld ? a.ld : a.batch);
+  const size_t B = (size_t)a.batch;
   const int N = a.N;
   const typename P::Par p = P::load(ParamSrc{as_uniform(a.ps), a.pb, a.pmask, B, b});
   double lb[NC], ub[NC];
@@ -972,10 +970,9 @@ __global__ void k_tu_at(int nq, const double* __restrict__ tq, const double* __r
 // ---------------------------------------------------------------------------------------
 __global__ void k_fbs_advance(int batch, int sweep, int nparts, const double* __restrict__ metric,
                               int* __restrict__ anyvalid, int* __restrict__ usel, int* __restrict__ status,
-                              double* __restrict__ maxChange, int* __restrict__ nactive, int ldb,
-                              const int* __restrict__ gate) {
+                              double* __restrict__ maxChange, int* __restrict__ nactive, const int* __restrict__ gate) {
   if (gate && *gate == 0) return;  // a sweep enqueued ahead of the verdict of the one before, which was the last
-  const size_t ld = (size_t)(ldb ? ldb : batch);  // row distance of metric / maxChange
+  const size_t B = (size_t)batch;  // row distance of metric / maxChange
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   bool still = false;
   if (b < batch) {
@@ -985,21 +982,21 @@ __global__ void k_fbs_advance(int batch, int sweep, int nparts, const double* __
     for (; q + 32 <= nparts; q += 32) {  // 32 independent loads in flight: the kernel is a few waves of pure latency
       double m[32];
 #pragma unroll
-      for (int j = 0; j < 32; ++j) m[j] = metric[(size_t)(q + j) * ld + b];
+      for (int j = 0; j < 32; ++j) m[j] = metric[(size_t)(q + j) * B + b];
 #pragma unroll
       for (int j = 0; j < 32; ++j) mx = fmax(mx, m[j]);
     }
     for (; q + 8 <= nparts; q += 8) {
       double m[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) m[j] = metric[(size_t)(q + j) * ld + b];
+      for (int j = 0; j < 8; ++j) m[j] = metric[(size_t)(q + j) * B + b];
 #pragma unroll
       for (int j = 0; j < 8; ++j) mx = fmax(mx, m[j]);
     }
-    for (; q < nparts; ++q) mx = fmax(mx, metric[(size_t)q * ld + b]);
+    for (; q < nparts; ++q) mx = fmax(mx, metric[(size_t)q * B + b]);
     if (mx < 0.0) mx = __builtin_nan("");
     if (status[b] == 0) {
-      maxChange[(size_t)(sweep - 1) * ld + b] = mx;  // the value :109 prints
+      maxChange[(size_t)(sweep - 1) * B + b] = mx;  // the value :109 prints
       if (mx <= 1.0) {                                   // :110
         status[b] = sweep;
       } else {

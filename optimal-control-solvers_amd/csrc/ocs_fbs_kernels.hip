@@ -35,9 +35,9 @@ static inline int hip_rc3(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 static PchipTab make_tab(const FbsTables& t) { return PchipTab{t.n, t.TN, t.HN, t.W1, t.W2, t.IH}; }
 
 int launch_pchip_mid(const FbsTables& t, int nrows, int ld, int batch, const double* V, double* out, hipStream_t s,
-                     int ldb, const int* gate) {
+                     const int* gate) {
   k_pchip_mid<<<dim3((batch + 255) / 256, (t.n - 1 + kPchipRun - 1) / kPchipRun), dim3(256), 0, s>>>(
-      make_tab(t), nrows, ld, batch, t.TM, V, out, ldb, gate);
+      make_tab(t), nrows, ld, batch, t.TM, V, out, gate);
   return hip_rc3(hipGetLastError());
 }
 
@@ -62,21 +62,20 @@ static void run_costate(const CostateArgs& a, hipStream_t s) {
   k_costate<P, 4><<<dim3((a.batch + 63) / 64), dim3(64), 0, s>>>(a);
 }
 int launch_costate(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* xmid,
-                   const double* u, const int* frozen, double* dump, double* lam, hipStream_t s, int ldb,
-                   const double* PR, const int* gate) {
+                   const double* u, const int* frozen, double* dump, double* lam, hipStream_t s, const double* PR,
+                   const int* gate) {
   if (frozen && !dump) return -1;
   if (p.functor == Functor::User && !xmid) {
-    if (ldb != 0 && ldb != batch) return -1;
     return user_vector(p.user) ? launch_costate_vscan(p, g, batch, x, ldx, PR, u, frozen, lam, s, gate)
                                : launch_costate_scan_u(p, g, batch, x, ldx, PR, u, frozen, lam, s, gate);
   }
   // the wave-specialised kernel while its workgroups (one per 64/nS instances) fit on the chip in two rounds
   // (launch_costate_pl has no gate: a gated pass with the midpoints given takes the lane kernel below)
   if (p.functor != Functor::User && costate_forms_midpoints(p, g.N, batch) && !(xmid && gate))
-    return xmid ? launch_costate_pl(p, g, batch, x, ldx, xmid, frozen, dump, lam, ldb, s)
-                : launch_costate_plx(p, g, batch, x, ldx, PR, frozen, dump, lam, ldb, s, gate);
+    return xmid ? launch_costate_pl(p, g, batch, x, ldx, xmid, frozen, dump, lam, s)
+                : launch_costate_plx(p, g, batch, x, ldx, PR, frozen, dump, lam, s, gate);
   if (!xmid) return -1;
-  CostateArgs a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, xmid, u, frozen, dump, lam, ldb};
+  CostateArgs a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, xmid, u, frozen, dump, lam};
   a.gate = gate;
   if (p.functor == Functor::User) {
     void* args[] = {(void*)&a};
@@ -94,9 +93,9 @@ static void run_control_grid(const ControlGridArgs& a, hipStream_t s) {
 int control_grid_parts(int N) { return (N + kPchipRun - 1) / kPchipRun; }
 int launch_control_grid(const ProblemDesc& p, const GridDesc& g, const FbsTables& t, int batch, const double* x, int ldx,
                         const double* xmid, const double* lam, double* u, const int* status, double* metric,
-                        double relTol, double absTol, hipStream_t s, int ldb, const int* gate, double relax) {
+                        double relTol, double absTol, hipStream_t s, const int* gate, double relax) {
   const ControlGridArgs a{g.N, batch, g.TU, p.ps, p.pb, p.pmask, p.lb, p.ub, x, ldx, xmid, lam, make_tab(t), t.TM, u,
-                          status, metric, relTol, absTol, ldb, gate, relax};
+                          status, metric, relTol, absTol, gate, relax};
   if (p.functor == Functor::User) {
     void* args[] = {(void*)&a};
     if (p.nS > 4 && !xmid) return -1;   // (no costate kernel of these shapes leaves the midpoints of x to this one: OWNX is not instantiated)
@@ -198,9 +197,9 @@ int launch_control_pts_sorted(const ProblemDesc& p, const FbsTables& t, int nq, 
   return hip_rc3(hipGetLastError());
 }
 int launch_fbs_advance(int batch, int sweep, int nparts, const double* metric, int* anyvalid, int* usel, int* status,
-                       double* maxChange, int* nactive, hipStream_t s, int ldb, const int* gate) {
+                       double* maxChange, int* nactive, hipStream_t s, const int* gate) {
   k_fbs_advance<<<dim3((batch + 63) / 64), dim3(64), 0, s>>>(batch, sweep, nparts, metric, anyvalid, usel, status,
-                                                                 maxChange, nactive, ldb, gate);
+                                                                 maxChange, nactive, gate);
   return hip_rc3(hipGetLastError());
 }
 

@@ -32,7 +32,6 @@
 #include "ocs_problems.hpp"
 #include "ocs_scan_kernel.hpp"
 #include <cstdio>
-#include <cstdlib>
 
 namespace ocs {
 
@@ -89,9 +88,7 @@ constexpr int kFcsCH = 4;   // chunks per wave (the four 16-lane rows)
 
 // W waves per workgroup of 16 trajectories, L steps per chunk: a superblock is 4 W L steps.
 // NKS: k-steps of the expansion (4 basis functions each); the gradient has NRT = ceil(NKS / 4) tiles of 16 functions.
-// ABL (diagnostic builds, -DOCS_FCS_ABL): 1 no expansion products, 2 no contraction products, 3 neither, 4 no barrier,
-// 5 no phase 3, 6 no phase 1
-template <class P, int W, int L, int NKS, int ABL = 0>
+template <class P, int W, int L, int NKS>
 __global__ __launch_bounds__(W * 64, (NKS > 4 ? 1024 : 2048) / (W * 64)) void k_backward_fcs(const BwdArgsFcs a) {
   constexpr int NAUG = P::NAUG, CH = kFcsCH, SB = W * CH * L, NRT = (NKS + 3) / 4, NSET = (2 * L + 1 + 3) / 4;
   constexpr int NRD = (CH * L + 1 + 7) / 8;   // record DMAs per wave and superblock (8 records each)
@@ -190,12 +187,7 @@ __global__ __launch_bounds__(W * 64, (NKS > 4 ? 1024 : 2048) / (W * 64)) void k_
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
-        for (int t = 0; t < NSET; ++t) {
-          if (ABL == 1 || ABL == 3)
-            e[t] += d4_fw{aE[t][ks], vB[ks], aE[t][ks], vB[ks]};
-          else
-            e[t] = mma_fw(aE[t][ks], vB[ks], e[t]);
-        }
+        for (int t = 0; t < NSET; ++t) e[t] = mma_fw(aE[t][ks], vB[ks], e[t]);
 #pragma unroll
       for (int t = 0; t < NSET; ++t) {
         if (4 * t + 0 <= 2 * L) uu[4 * t + 0] = e[t].x;
@@ -215,10 +207,6 @@ __global__ __launch_bounds__(W * 64, (NKS > 4 ? 1024 : 2048) / (W * 64)) void k_
     double al[L], be[L];
 #pragma unroll
     for (int q = 0; q < L; ++q) {
-      if (ABL == 6) {
-        al[q] = uu[2 * q + 2] + d.x[q]; be[q] = 1.0;
-        continue;
-      }
       const Rc c = rec_of(rw, q);
       const double xi = d.x[q], uA = uu[2 * q], uM = uu[2 * q + 1], uB = uu[2 * q + 2];
       double f = P::g_row_f(xi, uA, c.tA, rp);                 // compute_states :39-46
@@ -269,7 +257,7 @@ __global__ __launch_bounds__(W * 64, (NKS > 4 ? 1024 : 2048) / (W * 64)) void k_
     const double EB = g == 0 ? 0.0 : g == 1 ? eB : g == 2 ? p01B : e3B;
     if (g == 0) sm[sb & 1][wave][n] = double2{TA, TB};
     FCS_T(3);   // maps inside the wave
-    if (ABL != 4) lds_barrier_sc();
+    lds_barrier_sc();
     FCS_T(4);   // barrier
     // ---------------- phase 2: lam at the top of this chunk ----------------
     double lam = (sb == 0) ? 0.0 : csm[(sb & 1) ^ 1][n];
@@ -291,10 +279,6 @@ __global__ __launch_bounds__(W * 64, (NKS > 4 ? 1024 : 2048) / (W * 64)) void k_
     double col[2 * L], ctop = 0.0, pk1[L], p4s[L];
 #pragma unroll
     for (int q = 0; q < L; ++q) {
-      if (ABL == 5) {
-        p4s[q] = lt[q]; col[2 * q + 1] = al[q]; pk1[q] = be[q];
-        continue;
-      }
       const Rc c = rec_of(rw, q);
       const double xi = d.x[q], uA = uu[2 * q], uM = uu[2 * q + 1], uB = uu[2 * q + 2];
       double f = P::g_row_f(xi, uA, c.tA, rp);
@@ -342,12 +326,7 @@ __global__ __launch_bounds__(W * 64, (NKS > 4 ? 1024 : 2048) / (W * 64)) void k_
 #pragma unroll
     for (int m = 0; m < 2 * L; ++m)
 #pragma unroll
-      for (int rt = 0; rt < NRT; ++rt) {
-        if (ABL == 2 || ABL == 3)
-          acc[rt] += d4_fw{aC[m][rt], col[m], aC[m][rt], col[m]};
-        else
-          acc[rt] = mma_fw(aC[m][rt], col[m], acc[rt]);
-      }
+      for (int rt = 0; rt < NRT; ++rt) acc[rt] = mma_fw(aC[m][rt], col[m], acc[rt]);
     if (sb == 0 && wave == 0) {   // column 2N, from the topmost chunk
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt)
@@ -430,14 +409,6 @@ static void run_forward_fcw(const FwdArgsP2& a, bool uniform, hipStream_t s) {
 template <class P, int NKS>
 static void run_backward_fcs(const BwdArgsFcs& a, hipStream_t s) {
   const dim3 grid((a.batch + 15) / 16), block(kFcsW * 64);
-#ifdef OCS_FCS_ABL
-  static const int abl = getenv("OCS_FCS_ABL") ? atoi(getenv("OCS_FCS_ABL")) : 0;
-  if (NKS == 4) {
-#define OCS_ABL_CASE(K) if (abl == K) return (void)(k_backward_fcs<P, kFcsW, kFcsL, 4, K><<<grid, block, 0, s>>>(a));
-    OCS_ABL_CASE(1) OCS_ABL_CASE(2) OCS_ABL_CASE(3) OCS_ABL_CASE(4) OCS_ABL_CASE(5) OCS_ABL_CASE(6)
-#undef OCS_ABL_CASE
-  }
-#endif
   k_backward_fcs<P, kFcsW, kFcsL, NKS><<<grid, block, 0, s>>>(a);
 }
 
@@ -445,7 +416,7 @@ static void run_backward_fcs(const BwdArgsFcs& a, hipStream_t s) {
 int launch_forward_fcw(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, int ldbt, const double* BT,
                        const double* v, const double* x0, double* ck, double* J, hipStream_t s) {
   if (!fused_wave_supported(p.functor, p.nS, p.nC, nBasis, g.N, batch) || ldbt < 4 * ((nBasis + 3) / 4)) return -1;
-  FwdArgsP2 a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, nullptr, ck, J, nullptr, 0, 1, nullptr};
+  FwdArgsP2 a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, nullptr, ck, J, nullptr, 1, nullptr};
   a.BT = BT; a.v = v; a.nBasis = nBasis; a.ldbt = ldbt;
   switch ((nBasis + 3) / 4) {
     case 1: run_forward_fcw<LogisticK<1>, 1>(a, g.uniform, s); break;

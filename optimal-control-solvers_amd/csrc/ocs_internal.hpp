@@ -89,7 +89,7 @@ bool costate_pl_ok(Functor f, int nS, int nC, int N, int batch);
 // the same forming the pchip midpoints of x itself (no xmid array); PR: [N][costate_prec()] interval records
 int costate_prec();
 int launch_costate_plx(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* PR,
-                       const int* frozen, double* dump, double* lam, int ld, hipStream_t s, const int* gate = nullptr);
+                       const int* frozen, double* dump, double* lam, hipStream_t s, const int* gate = nullptr);
 // the same pass as a scan over time (ocs_costate_scan_kernel.hpp); _met: with the convergence test of the folded sweep
 bool costate_scan_ok(const ProblemDesc& p, const GridDesc& g, int batch);
 bool costate_scan_u_ok(const ProblemDesc& p, const GridDesc& g, int batch);
@@ -105,18 +105,14 @@ int launch_costate_scan_met(const ProblemDesc& p, const GridDesc& g, int batch, 
                             const double* lb, const double* ub, double relTol, double absTol, int sweep, int* status,
                             double* maxChange, int* nactive, double* lam, hipStream_t s, const int* gate);
 int launch_costate_pl(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* xmid,
-                      const int* frozen, double* dump, double* lam, int ld, hipStream_t s);
+                      const int* frozen, double* dump, double* lam, hipStream_t s);
 // pend0: optional [B], the k1 half of column 2N of dJdu when the steps above N were integrated by another kernel
 int launch_backward_pl(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
                        const double* lamT, double* lam, double* dJdu, double* lam0, const double* pend0,
                        hipStream_t s);
 // the same pass with a minimal recursion wave (ocs_pipeline2_kernels.hip)
 int launch_forward_p2(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
-                      double* x, double* J, const int* frozen, int ld, hipStream_t s, bool no_cost_row,
-                      const int* gate);
-int launch_forward_pl(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
-                      double* x, double* J, const int* frozen, double* dump, int ld, hipStream_t s,
-                      bool no_cost_row = false, const int* gate = nullptr);
+                      double* x, double* J, const int* frozen, hipStream_t s, bool no_cost_row, const int* gate);
 // whether launch_forward with these shapes runs the one kernel that honours FwdOpts::gate
 bool forward_gate_supported(const ProblemDesc& p, const GridDesc& g, int batch);
 // workgroups (of 64/nS trajectories) up to which fb_sweep takes its wave-specialised kernels (the folded two-kernel sweep, the
@@ -150,8 +146,6 @@ struct FwdOpts {
   const double* Jadd = nullptr; // J = Jadd + x(end,end)
   const int* frozen = nullptr;  // [B]: trajectories with frozen[b] != 0 store nothing (fb_sweep: converged instances)
   double* dump = nullptr;       // [B] scratch the stores of frozen trajectories go to
-  int ld = 0;                   // row distance of the batch-minor arrays when the call covers a window of a larger
-                                // batch (pointers offset by the caller, `batch` = size of the window); 0 = batch
   const int* gate = nullptr;    // device flag: the launch does nothing if *gate == 0 (only where
                                 // forward_gate_supported says so; otherwise the call fails)
   bool no_cost_row = false;     // the running-objective row of x may be left unwritten (only J is wanted); honoured
@@ -238,9 +232,8 @@ struct FbsTables {   // pchip node tables of an integrator grid, device pointers
   const double* IH;  // [n-1] reciprocal spacings
   const double* PR;  // [n-1][costate_prec()] per-interval pchip records (launch_costate_plx)
 };
-// ldb: row distance of V / out when the call covers a window of a larger batch (0 = batch)
 int launch_pchip_mid(const FbsTables& t, int nrows, int ld, int batch, const double* V, double* out, hipStream_t s,
-                     int ldb = 0, const int* gate = nullptr);
+                     const int* gate = nullptr);
 bool costate_forms_midpoints(const ProblemDesc& p, int N, int batch);
 // fb_sweep with the control update folded into the state pass (ocs_fold_kernel.hpp) and the convergence test into the
 // costate pass (k_costate_plx, MET): sweeps >= 2 are two kernels
@@ -252,7 +245,7 @@ int launch_costate_met(const ProblemDesc& p, const GridDesc& g, int batch, const
                        const double* lb, const double* ub, double relTol, double absTol, int sweep, int* status,
                        double* maxChange, int* nactive, double* lam, hipStream_t s, const int* gate);
 int launch_costate(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* xmid,
-                   const double* u, const int* frozen, double* dump, double* lam, hipStream_t s, int ldb = 0,
+                   const double* u, const int* frozen, double* dump, double* lam, hipStream_t s,
                    const double* PR = nullptr,   // xmid == NULL with PR: the kernel forms the midpoints (see below)
                    const int* gate = nullptr);
 // metric (optional): [control_grid_parts(N)][B] partial maxima of the weighted change at the grid nodes (error points
@@ -280,8 +273,7 @@ int launch_interp_pchip_sorted(const FbsTables& t, int nComp, const int* QS, con
                                const double* V, double* out, hipStream_t s);
 int launch_control_grid(const ProblemDesc& p, const GridDesc& g, const FbsTables& t, int batch, const double* x, int ldx,
                         const double* xmid, const double* lam, double* u, const int* status, double* metric,
-                        double relTol, double absTol, hipStream_t s, int ldb = 0, const int* gate = nullptr,
-                        double relax = 1.0);
+                        double relTol, double absTol, hipStream_t s, const int* gate = nullptr, double relax = 1.0);
 int launch_control_pts(const ProblemDesc& p, const FbsTables& t, int nq, const int* KQ, const double* SQ,
                        const double* TUQ, int batch, const double* x, int ldx, const double* lam, double* out,
                        const int* usel, long long odelta, double* metric, int* anyvalid, double relTol,
@@ -297,7 +289,7 @@ int launch_tu_at(const ProblemDesc& p, int nq, const double* tq, double* TUQ, hi
 int control_pts_parts(int nq);  // rows of the partial-maximum array `metric` [parts][B] that launch_control_pts fills
 int launch_fbs_init(int batch, int nsweeps, int* usel, int* status, double* maxChange, hipStream_t s);
 int launch_fbs_advance(int batch, int sweep, int nparts, const double* metric, int* anyvalid, int* usel, int* status,
-                       double* maxChange, int* nactive, hipStream_t s, int ldb = 0, const int* gate = nullptr);
+                       double* maxChange, int* nactive, hipStream_t s, const int* gate = nullptr);
 
 // registry queries (host)
 bool functor_supported(Functor f, int nS, int nC);

@@ -95,12 +95,12 @@ static std::vector<std::string> kernel_names(int nS, int nC, bool rowsep, bool f
   if (rowsep) {   // (entries left empty are not compiled)
     n[UK_FWD_P2_X] = "ocs::k_forward_p2<ocs::UserP, true, true, false, 0>";
     n[UK_FWD_P2_J] = "ocs::k_forward_p2<ocs::UserP, false, true, false, 0>";
-    n[UK_SCAN_LAM_DJDU] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, true, false, 0>";
-    n[UK_SCAN_LAM] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, false, false, 0>";
-    n[UK_SCAN_DJDU] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", false, true, false, 0>";
-    n[UK_SCAN_LAM_DJDU_LT] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, true, true, 0>";
-    n[UK_SCAN_LAM_LT] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, false, true, 0>";
-    n[UK_SCAN_DJDU_LT] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", false, true, true, 0>";
+    n[UK_SCAN_LAM_DJDU] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, true, false>";
+    n[UK_SCAN_LAM] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, false, false>";
+    n[UK_SCAN_DJDU] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", false, true, false>";
+    n[UK_SCAN_LAM_DJDU_LT] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, true, true>";
+    n[UK_SCAN_LAM_LT] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", true, false, true>";
+    n[UK_SCAN_DJDU_LT] = "ocs::k_backward_scan<ocs::UserP, " + wl + ", false, true, true>";
   }
   if (rowsep) n[UK_COSTATE_SCAN_U] = "ocs::k_costate_scan<ocs::UserP, " + wl + ", false, true>";
   if (fold) {

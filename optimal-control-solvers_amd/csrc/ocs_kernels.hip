@@ -231,8 +231,7 @@ int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const dou
   const bool plain = !o.uconst && !o.Jadd;
   // (MAP_SCAN names the adjoint kernel; the state pass of such an integrator is chosen automatically)
   int map = choose_mapping(p, g.N, batch, o.mapping == MAP_SCAN ? MAP_AUTO : o.mapping, plain, false, x != nullptr);
-  if (map == MAP_ROWSPLIT && (o.frozen || o.ld) && o.mapping == MAP_AUTO) map = MAP_LANE;  // not in that kernel
-  if (map == MAP_PIPELINE && forward_is_vector(p) && o.ld && o.mapping == MAP_AUTO) map = MAP_LANE;
+  if (map == MAP_ROWSPLIT && o.frozen && o.mapping == MAP_AUTO) map = MAP_LANE;  // not in that kernel
   if (map == MAP_PIPELINE) {
     const int N1 = plain ? pipeline_steps(p, g.N, batch, false) : 0;
     if (N1 == 0 || (N1 < g.N && !x)) return -1;  // the split needs the boundary column in memory
@@ -241,19 +240,17 @@ int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const dou
     // (a split pass hands the running objective to the lane kernel through the boundary column: keep the row then)
     int rc;
     if (forward_is_vector(p)) {
-      if (o.ld) return -1;
       rc = launch_forward_pv(p, g1, batch, x0, u, x, J, s, o.no_cost_row && N1 == g.N, o.gate, o.frozen);
     } else {
-      rc = launch_forward_pl(p, g1, batch, x0, u, x, J, o.frozen, o.dump, o.ld, s, o.no_cost_row && N1 == g.N, o.gate);
+      if (o.frozen && !o.dump) return -1;  // the lane kernel that finishes a split pass stores to dump
+      rc = launch_forward_p2(p, g1, batch, x0, u, x, J, o.frozen, s, o.no_cost_row && N1 == g.N, o.gate);
     }
     if (rc || N1 == g.N) return rc;
     // remaining steps N1 .. N-1 on the lane kernel, continuing from column N1 (state rows and running objective)
-    const size_t ldb = o.ld ? o.ld : batch;
-    const size_t col = (size_t)(p.nS + 1) * ldb, ucol = (size_t)p.nC * ldb;
+    const size_t col = (size_t)(p.nS + 1) * batch, ucol = (size_t)p.nC * batch;
     double* xb = x + (size_t)N1 * col;
     FwdArgs a{g.N - N1, batch, g.REC + (size_t)N1 * rec_stride_host(functor_ntc(p.functor, p.nS)), p.ps, p.pb,
-              p.pmask, xb, u + (size_t)(2 * N1) * ucol, xb, J, nullptr, o.frozen, o.dump, xb + (size_t)p.nS * ldb,
-              o.ld};
+              p.pmask, xb, u + (size_t)(2 * N1) * ucol, xb, J, nullptr, o.frozen, o.dump, xb + (size_t)p.nS * batch};
     a.gate = o.gate;
     if (p.functor == Functor::User) {
       void* args[] = {(void*)&a};
@@ -263,11 +260,11 @@ int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const dou
     return hip_rc(hipGetLastError());
   }
   if (map == MAP_ROWSPLIT) {
-    if (!plain || o.frozen || o.ld || !rowsplit_supported(p.functor, p.nS, p.nC)) return -1;
+    if (!plain || o.frozen || !rowsplit_supported(p.functor, p.nS, p.nC)) return -1;
     return launch_forward_rs(p, g, batch, x0, u, x, J, s);
   }
   if (o.uconst && !x) return -1;
-  FwdArgs a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, o.Jadd, o.frozen, o.dump, nullptr, o.ld};
+  FwdArgs a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, o.Jadd, o.frozen, o.dump, nullptr};
   a.gate = o.gate;
   if (p.functor == Functor::User) {
     void* args[] = {(void*)&a};

@@ -21,9 +21,9 @@
 //
 // One LDS-only barrier per block of D = 8 steps.  Interval k (between barriers k and k+1):
 //   M: issues block k+1+Q, waits for block k+2    P: prepares block k+1    S: block k    C: block k-1    J: block k-2
-// Results: the arithmetic of a step is that of k_forward_pl (same formulas, same association) -- the recursion on
-// z and the objective summed over rows before the quadrature weights (Numerics) -- to round-off the
-// lane kernels' and the oracle's.
+// Results: a step is the recursion on z and the objective summed over rows before the quadrature weights (DESIGN.md,
+// Numerics; generic row functions: the reference's sum, RK4Integrator.m:50) -- to round-off the lane kernels' and the
+// oracle's.  The state pass of the folded sweep (ocs_fold_kernel.hpp) repeats this arithmetic.
 // This header holds the kernel template only (also compiled by hipRTC for user problems given as row functions); the
 // launchers are in ocs_pipeline2_kernels.hip.  Registry problems use the shifted form of their rows (HAS_SHIFT), user
 // problems the generic g_row_f / g_row_q.
@@ -135,7 +135,6 @@ struct FwdArgsP2 {
   double* x;
   double* J;
   const int* frozen;   // optional [B]: trajectories with frozen[b] != 0 store nothing
-  int ld;              // row distance of the arrays (window of a larger batch) or 0
   int nocost;          // leave the running-objective row of x unwritten (J only)
   const int* gate;     // optional: the launch does nothing if *gate == 0
   // NKS > 0 (u expanded in the kernel; `u` is not read):
@@ -160,11 +159,11 @@ __global__ __launch_bounds__((P2Cfg<P::NS, NKS, TPW_>::NWAVE * 64)) void k_forwa
   __shared__ double dd[2][D][TPW];                                        // objective increments of a block
   const int wave = C_::role(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
-  const size_t B = (size_t)(a.ld ? a.ld : a.batch);
+  const size_t B = (size_t)a.batch;
   const int nb = a.N / D;
   // A batch that is not a multiple of the tile: the LAST workgroup takes the last TPW trajectories, overlapping its neighbour --
   // the overlap is computed twice with the same operations and stored twice with the same values (nothing of this kernel is
-  // accumulated across trajectories).  The launcher asks for it only with batch >= TPW and an even row distance (the 16-byte
+  // accumulated across trajectories).  The launcher asks for it only with batch >= TPW and an even batch (the 16-byte
   // DMA chunks stay aligned).
   const int bw_ = blockIdx.x * TPW;
   const int bw = bw_ + TPW <= a.batch ? bw_ : a.batch - TPW;

@@ -37,7 +37,7 @@ static void run_forward_pv(const FwdArgsP2& a, hipStream_t s) {
 int launch_forward_pv(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u, double* x,
                       double* J, hipStream_t s, bool no_cost_row, const int* gate, const int* frozen) {
   if (!vector_problem_ok(p) || g.N < 8 || g.N % 8 != 0 || batch < 64 || !tile_ok(batch, 64)) return -1;
-  const FwdArgsP2 a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, frozen, 0, no_cost_row ? 1 : 0, gate};
+  const FwdArgsP2 a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, frozen, no_cost_row ? 1 : 0, gate};
   if (p.functor == Functor::User) {
     void* args[] = {(void*)&a};
     return jit_launch(p.user, x ? UK_FWD_PV_X : UK_FWD_PV_J, dim3(tile_count(batch, 64)), dim3(kPvWaves * 64), args, s);
@@ -79,12 +79,10 @@ static void run_forward_p2(const FwdArgsP2& a, bool uniform, hipStream_t s) {
 }
 
 int launch_forward_p2(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
-                      double* x, double* J, const int* frozen, int ld, hipStream_t s, bool no_cost_row,
-                      const int* gate) {
+                      double* x, double* J, const int* frozen, hipStream_t s, bool no_cost_row, const int* gate) {
   if (!pipeline_problem_ok(p) || !pipeline_shape_ok(p.nS, g.N, batch, false)) return -1;
-  if (batch % (64 / p.nS) != 0 && (ld ? ld : batch) % 2 != 0) return -1;   // (ragged last tile: even row distance only)
   if (p.functor == Functor::User) {   // the hipRTC instances of the same kernel template (generic row functions)
-    const FwdArgsP2 au{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, frozen, ld, no_cost_row ? 1 : 0, gate};
+    const FwdArgsP2 au{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, frozen, no_cost_row ? 1 : 0, gate};
     static_assert(p2_waves(1) == P2Cfg<1>::NWAVE && p2_waves(2) == P2Cfg<2>::NWAVE && p2_waves(4) == P2Cfg<4>::NWAVE,
                   "launch shape of the hipRTC instances");
     const int TPW = 64 / p.nS, nwave = p2_waves(p.nS);
@@ -92,7 +90,7 @@ int launch_forward_p2(const ProblemDesc& p, const GridDesc& g, int batch, const 
     return jit_launch(p.user, x ? UK_FWD_P2_X : UK_FWD_P2_J, dim3((batch + TPW - 1) / TPW), dim3(nwave * 64), args, s,
                       p.nS == 1 ? 0u : 48u * 1024u);
   }
-  const FwdArgsP2 a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, frozen, ld, no_cost_row ? 1 : 0, gate};
+  const FwdArgsP2 a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, frozen, no_cost_row ? 1 : 0, gate};
   if (p.nS == 1)
     run_forward_p2<LogisticK<1>>(a, g.uniform, s);
   else if (p.nS == 2)

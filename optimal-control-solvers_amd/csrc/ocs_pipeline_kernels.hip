@@ -12,31 +12,22 @@
 //
 //   (roles are cut where the hand-off is narrow: LDS stores cost a lone wave ~13 cycles per 512 B, as
 //    much as two fp64 instructions, so R hands over 3 values per step and A 3, not 8 and 4)
-//   forward   wave M: memory wave.  Streams control samples and step records HBM -> LDS with LDS-DMA
-//                     (global_load_lds_dwordx4, 1 KiB per instruction, no VGPR staging), Q blocks
-//                     ahead of the compute waves; it is the only wave that waits on loads.
-//             wave S: the state recursion (F1..F4, Y2..Y4, y_{i+1}) out of LDS; stores the state
-//                     rows; publishes the four stage states of every step.
-//             wave C: integrates the objective from the published stage states, reduces it over
-//                     the rows of a trajectory (DPP) and stores the cost row / J.
-//   backward  wave M: streams checkpoints, control samples and records.
+//   forward   k_forward_p2 (ocs_pipeline2_kernel.hpp): its own roles around a minimal recursion wave.
+//   backward  wave M: memory wave.  Streams checkpoints, control samples and step records HBM -> LDS
+//                     with LDS-DMA (global_load_lds_dwordx4, 1 KiB per instruction, no VGPR staging),
+//                     Q blocks ahead of the compute waves; it is the only wave that waits on loads.
 //             wave R: recomputes the stage states Y2..Y4 from the checkpoints, publishes them.
 //             wave A: the adjoint recursion (dJdk, lam); stores lam; publishes k1, k2+k3, k4.
 //             wave D: assembles the dJdu columns from k1..k4, reduces over rows, stores them.
 //
 // The serial critical path per step shrinks to the longest role, and no compute wave ever waits for
 // HBM.  Arithmetic inside the roles is the row-split kernels' (same formulas, same association), so
-// the two mappings agree bit for bit; layouts and semantics are those of k_forward / k_backward
+// the two mappings agree bit for bit; layouts and semantics are those of k_backward
 // (RK4Integrator.m:28-121).  Restrictions (the launcher falls back to row-split otherwise):
 // nSTEPS a multiple of D, batch a multiple of 64/G.
 #include "ocs_device_common.hpp"
 #include "ocs_internal.hpp"
 #include "ocs_problems.hpp"
-#include <cstdlib>
-#ifdef OCS_PL_STAMPS
-#include <cstdio>
-#include <vector>
-#endif
 
 namespace ocs {
 
@@ -48,13 +39,6 @@ __device__ static inline double dpp_quad_pl(double v) {
   const int lo2 = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
   const int hi2 = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi2, lo2);
-}
-template <int G>
-__device__ static inline double group_sum_pl(double v) {
-  static_assert(G == 1 || G == 2 || G == 4, "group size");
-  if (G >= 2) v += dpp_quad_pl<0xB1>(v);
-  if (G == 4) v += dpp_quad_pl<0x4E>(v);
-  return v;
 }
 
 // Hand-off barrier: only LDS traffic has to be complete.  __syncthreads() would also drain vmcnt,
@@ -79,453 +63,25 @@ __device__ static inline void wait_blocks(int blocks) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPB) : "memory");
 }
 
-template <int G, bool BWD>
+template <int G>
 struct PLCfg {
   static constexpr int D = 8;                          // steps per hand-off block (BASELINE N = 1000 = 125 blocks)
   static constexpr int TPW = 64 / G;                   // trajectories per workgroup
   static constexpr int Q = 3;                          // blocks the memory wave runs ahead (wait_blocks: <= 2 younger)
-  static constexpr int LAG = BWD ? 2 : 1;              // intervals between the first and the last reader of a slot
-  static constexpr int NSLOT = Q + LAG + 1;            // input ring slots (see the schedules below)
+  static constexpr int LAG = 2;                        // intervals between the first and the last reader of a slot
+  static constexpr int NSLOT = Q + LAG + 1;            // input ring slots (see the schedule below)
   static constexpr int RS = rec_stride(1);             // doubles per step record (NTC = 1)
   static constexpr int SCO = rec_sc_offset(1);         // offset of the step constants in a record
   static constexpr int REC_DBL = D * RS;               // records of a block
   static constexpr int NREC = REC_DBL / 128;           // DMA instructions for them
   static constexpr int U_DBL = 2 * D * TPW;            // control samples of a block
   static constexpr int NU = U_DBL / 128;
-  static constexpr int X_DBL = BWD ? D * 64 : 0;       // checkpoint rows of a block (backward only)
+  static constexpr int X_DBL = D * 64;                 // checkpoint rows of a block
   static constexpr int NX = X_DBL / 128;
   static constexpr int SLOT = REC_DBL + U_DBL + X_DBL;
   static constexpr int LPB = NREC + NU + NX;           // DMA instructions per block
   static_assert(REC_DBL % 128 == 0 && U_DBL % 128 == 0, "blocks must be whole DMA instructions");
 };
-
-#ifdef OCS_PL_STAMPS
-#define PL_T() __builtin_amdgcn_s_memtime()
-#else
-#define PL_T() 0LL
-#endif
-
-struct FwdArgsPL {
-  int N, batch;
-  const double* REC;
-  const double* ps;
-  const double* pb;
-  unsigned pmask;
-  const double* x0;
-  const double* u;
-  double* x;
-  double* J;
-  long long* dbg;  // diagnostic build (-DOCS_PL_STAMPS) only: per-workgroup cycle sums; nullptr otherwise
-  const int* frozen;  // optional [B]: trajectories with frozen[b] != 0 store nothing (as in FwdArgs)
-  double* dump;       // [B] scratch for their stores
-  int ld;             // row distance of the arrays when the launch covers a window of a larger batch; 0 = batch
-  int nocost;         // leave the running-objective row of x unwritten (J only)
-  const int* gate;    // optional: the launch does nothing if *gate == 0 (a sweep enqueued before the previous one's
-                      // count of active instances is known, fb_sweep)
-};
-
-// ---------------------------------------------------------------------------------------
-// forward.  nb = N / D blocks.  barrier_k (k = 0..nb) separates interval k-1 from interval k and is
-// reached by M only once block k has landed in LDS.  In interval k
-//   M issues the DMA of block k+Q into input slot (k+Q) % NSLOT, then waits for block k+1;
-//   S processes block k     (inputs: slot k % NSLOT;        writes stage buffer k & 1);
-//   C processes block k-1   (inputs: slot (k-1) % NSLOT;    reads stage buffer (k-1) & 1).
-// The slot M overwrites in interval k last served block k+Q-NSLOT = k-2, read by C in interval k-1.
-// ---------------------------------------------------------------------------------------
-template <class P, bool OUT_X, bool FRZ>
-__global__ __launch_bounds__(192) void k_forward_pl(const FwdArgsPL a) {
-  constexpr int G = P::NS, NAUG = P::NAUG;
-  static_assert(P::NC == 1 && P::NTC == 1, "pipeline kernels are written for one control and one time coefficient");
-  using C_ = PLCfg<G, false>;
-  constexpr int D = C_::D, TPW = C_::TPW, Q = C_::Q, NSLOT = C_::NSLOT, RS = C_::RS, SCO = C_::SCO;
-  // [buffer][Y1..Y4][step][lane], the step stride padded so that the objective wave, whose lanes of a trajectory
-  // take consecutive steps, reads G rows of a step per lane without bank conflicts
-  // (pairs (Y1, Y2), (Y3, Y4): two 16-byte LDS instructions per step on the writing side; with 65 elements per step
-  //  the G lanes of a trajectory in C, one step apart, sit 16 bytes apart in the banks)
-  constexpr int SS = (G == 1) ? 64 : 65;
-  __shared__ __attribute__((aligned(16))) double2 stage[2][2][D][SS];
-  __shared__ double ulast[2][64];  // control sample at the first node of a block (S -> C)
-  __shared__ __attribute__((aligned(16))) double inp[NSLOT][C_::SLOT];  // [slot]{records | u}
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const size_t B = (size_t)(a.ld ? a.ld : a.batch);
-  const int nb = a.N / D;
-  const int bw = blockIdx.x * TPW;  // first trajectory of this workgroup
-  if (a.gate && *a.gate == 0) return;
-
-  if (wave == 0) {
-    // ---------------- M: HBM -> LDS ----------------
-    auto issue = [&](int j) OCS_INLINE {
-      double* dst = &inp[j % NSLOT][0];
-#pragma unroll
-      for (int q = 0; q < C_::NREC; ++q)
-        dma16(a.REC + (size_t)j * C_::REC_DBL + q * 128 + 2 * lane, dst + q * 128);
-#pragma unroll
-      for (int q = 0; q < C_::NU; ++q) {
-        const int e = q * 128 + 2 * lane, row = e / TPW, tl = e % TPW;
-        dma16(a.u + ((size_t)(2 * D * j + 1 + row)) * B + bw + tl, dst + C_::REC_DBL + q * 128);
-      }
-    };
-    for (int j = 0; j < Q && j < nb; ++j) issue(j);
-    long long tw = 0, tb = 0;
-    const long long t00 = PL_T();
-    for (int k = 0; k <= nb; ++k) {
-      const long long t0 = PL_T();
-      if (k < nb) {
-        const int behind = (nb - 1 - k) < (Q - 1) ? (nb - 1 - k) : (Q - 1);  // younger blocks in flight
-        wait_blocks<C_::LPB>(behind);
-      }
-      const long long t1 = PL_T();
-      lds_barrier();
-      const long long t2 = PL_T();
-      tw += t1 - t0;
-      tb += t2 - t1;
-      if (k + Q < nb) issue(k + Q);
-    }
-#ifdef OCS_PL_STAMPS
-    if (a.dbg && lane == 0) {
-      a.dbg[blockIdx.x * 16 + 0] = tw;
-      a.dbg[blockIdx.x * 16 + 1] = tb;
-      a.dbg[blockIdx.x * 16 + 2] = PL_T() - t00;
-    }
-#endif
-    (void)tw; (void)tb; (void)t00;
-  } else if (G == 1) {
-    // One row per trajectory: nothing to reduce across lanes and no redundant store; C sums the objective lane by
-    // lane and, having slack, also stores the state row (from Y1), so that S only marches.
-    const int r = lane % G;
-    const int tl = lane / G;
-    const int b = bw + tl;
-    const uniform_ptr PS = as_uniform(a.ps);
-    const typename P::RowPar rp = P::load_row([&](int k) OCS_INLINE {
-      return ((a.pmask >> k) & 1u) ? a.pb[(size_t)k * B + b] : PS[k];
-    }, r);
-    // a frozen trajectory writes every value to one scratch double (pointer stride 0): no branch around stores
-    // (FRZ is a template parameter: without frozen lanes the column stride stays a scalar)
-    // frozen trajectories skip their stores (a scratch address written a thousand times by the same lane was
-    // measured to cost up to 60 % of the kernel once most instances are frozen)
-    const bool fz = FRZ && a.frozen[b] != 0;
-    const size_t colB = (size_t)NAUG * B;
-    const double u0 = a.u[b];
-    if (wave == 1) {
-      // ---------------- S: state recursion ----------------
-      // the recursion runs on z = y - m_r/2 (P::row_f_shifted: two dependent operations per stage, not three)
-      const double mh = P::row_shift(rp);
-      const double y0 = a.x0[(size_t)r * B + b];
-      double y = y0 - mh;
-      double cprev = P::row_vertex(mh, u0);
-      long long tb = 0, tc = 0;
-      for (int k = 0; k <= nb; ++k) {
-        const long long t0 = PL_T();
-        lds_barrier();
-        const long long t1 = PL_T();
-        tb += t1 - t0;
-        if (k < nb) {
-          const double* rec = &inp[k % NSLOT][0];
-          const double* us = rec + C_::REC_DBL + tl;
-          double2* w = &stage[k & 1][0][0][lane];
-          // LDS reads of step s+1 are issued before step s is computed (LDS latency ~100 cycles would
-          // otherwise sit on every step: the scheduler keeps loads next to their uses)
-          struct In { double h, hh, h6, uM, uB; };
-          auto fetch = [&](int s) OCS_INLINE {
-            In v;
-            v.h = rec[RS * s];
-            v.hh = rec[RS * s + 1];
-            v.h6 = rec[RS * s + 2];
-            v.uM = us[(2 * s) * TPW];
-            v.uB = us[(2 * s + 1) * TPW];
-            return v;
-          };
-          In nxt = fetch(0);
-#pragma unroll
-          for (int s = 0; s < D; ++s) {
-            const In c = nxt;
-            if (s + 1 < D) nxt = fetch(s + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            const double cM = P::row_vertex(mh, c.uM), cB = P::row_vertex(mh, c.uB);
-            const double F1 = P::row_f_shifted(y, cprev);
-            double Y = __builtin_fma(c.hh, F1, y);
-            w[s * SS] = double2{y, Y};                     // (Y1, Y2) - m/2
-            const double F2 = P::row_f_shifted(Y, cM);
-            Y = __builtin_fma(c.hh, F2, y);
-            const double Y3 = Y;
-            const double F3 = P::row_f_shifted(Y, cM);
-            Y = __builtin_fma(c.h, F3, y);
-            w[(D + s) * SS] = double2{Y3, Y};              // (Y3, Y4) - m/2
-            const double F4 = P::row_f_shifted(Y, cB);
-            y = __builtin_fma(c.h6, F4, __builtin_fma(c.h6, __builtin_fma(2.0, F3, __builtin_fma(2.0, F2, F1)), y));  // (F4 joins last:
-            // one dependent operation after it instead of two)
-            cprev = cB;
-          }
-        }
-        tc += PL_T() - t1;
-      }
-#ifdef OCS_PL_STAMPS
-      if (a.dbg && lane == 0) {
-        a.dbg[blockIdx.x * 16 + 4] = tb;
-        a.dbg[blockIdx.x * 16 + 5] = tc;
-      }
-#endif
-      (void)tb; (void)tc;
-      if (OUT_X && !fz) a.x[((size_t)a.N * NAUG + r) * B + b] = y + mh;  // x(t_N); C stores the other nodes
-    } else {
-      // ---------------- C: objective ----------------
-      // pc += W_A q1 + W_M (q2 + q3) + W_B q4 with the quadrature weights of the record table
-      // (W_A = h/6 e^{-r t_A}, ...): the same sum as h/6 (F1 + 2 F2 + 2 F3 + F4) of the cost row.
-      const double mh = P::row_shift(rp);  // the stage values arrive as Y - m_r/2
-      double pc = 0.0, uprev2 = u0 * u0;
-      double* xc = a.x + (size_t)G * B + b;
-      double* xr = a.x + (size_t)r * B + b;
-      const bool wc = !fz && !a.nocost;  // the objective row is written
-      if (OUT_X && wc) *xc = 0.0;
-      long long tb = 0, tc = 0;
-      for (int k = 0; k <= nb; ++k) {
-        const long long t0 = PL_T();
-        lds_barrier();
-        const long long t1 = PL_T();
-        tb += t1 - t0;
-        if (k >= 1) {
-          const int j = k - 1;
-          const double* rec = &inp[j % NSLOT][0];
-          const double* us = rec + C_::REC_DBL + tl;
-          const double2* w = &stage[j & 1][0][0][lane];
-          struct In { double wA, wM, wB, uM, uB, Y1, Y2, Y3, Y4; };
-          auto fetch = [&](int s) OCS_INLINE {
-            In v;
-            v.wA = rec[RS * s + SCO + 3];
-            v.wM = rec[RS * s + SCO + 4];
-            v.wB = rec[RS * s + SCO + 5];
-            v.uM = us[(2 * s) * TPW];
-            v.uB = us[(2 * s + 1) * TPW];
-            const double2 p12 = w[s * SS], p34 = w[(D + s) * SS];
-            v.Y1 = p12.x;
-            v.Y2 = p12.y;
-            v.Y3 = p34.x;
-            v.Y4 = p34.y;
-            return v;
-          };
-          In nxt = fetch(0);
-#pragma unroll
-          for (int s = 0; s < D; ++s) {
-            const In c = nxt;
-            if (s + 1 < D) nxt = fetch(s + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            const double uM2 = c.uM * c.uM, uB2 = c.uB * c.uB;
-            const double y1 = c.Y1 + mh;
-            if (OUT_X) {
-              if (!fz) *xr = y1;   // x(t_i)
-              xr += colB;
-            }
-            const double q1 = P::row_q(y1, uprev2, rp), q2 = P::row_q(c.Y2 + mh, uM2, rp);
-            const double q3 = P::row_q(c.Y3 + mh, uM2, rp), q4 = P::row_q(c.Y4 + mh, uB2, rp);
-            pc = __builtin_fma(c.wA, q1, __builtin_fma(c.wM, q2 + q3, __builtin_fma(c.wB, q4, pc)));
-            if (OUT_X) {
-              xc += colB;
-              const double pcs = group_sum_pl<G>(pc);
-              if (wc) *xc = pcs;
-            }
-            uprev2 = uB2;
-          }
-        }
-        tc += PL_T() - t1;
-      }
-#ifdef OCS_PL_STAMPS
-      if (a.dbg && lane == 0) {
-        a.dbg[blockIdx.x * 16 + 8] = tb;
-        a.dbg[blockIdx.x * 16 + 9] = tc;
-      }
-#endif
-      (void)tb; (void)tc;
-      const double Jt = group_sum_pl<G>(pc);
-      if (!fz) a.J[b] = Jt;
-    }
-  } else if (wave == 1) {
-    // ---------------- S: state recursion ----------------
-    // Only the recursion: the stage states go to LDS, C stores the trajectory from there.  The recursion runs on
-    // z = y - m_r/2 (P::row_f_shifted: two dependent operations per stage instead of three).
-    const int r = lane % G;
-    const int tl = lane / G;
-    const int b = bw + tl;
-    const uniform_ptr PS = as_uniform(a.ps);
-    const typename P::RowPar rp = P::load_row([&](int k) OCS_INLINE {
-      return ((a.pmask >> k) & 1u) ? a.pb[(size_t)k * B + b] : PS[k];
-    }, r);
-    const bool fz = FRZ && a.frozen[b] != 0;
-    const double mh = P::row_shift(rp);
-    double uprev = a.u[b];
-    double y = a.x0[(size_t)r * B + b] - mh;
-    double cprev = P::row_vertex(mh, uprev);
-    long long tb = 0, tc = 0;
-    for (int k = 0; k <= nb; ++k) {
-      const long long t0 = PL_T();
-      lds_barrier();
-      const long long t1 = PL_T();
-      tb += t1 - t0;
-      if (k < nb) {
-        const double* rec = &inp[k % NSLOT][0];
-        const double* us = rec + C_::REC_DBL + tl;
-        double2* w = &stage[k & 1][0][0][lane];
-        ulast[k & 1][lane] = uprev;
-        // LDS reads of step s+1 are issued before step s is computed (LDS latency ~100 cycles would
-        // otherwise sit on every step: the scheduler keeps loads next to their uses)
-        struct In { double h, hh, h6, uM, uB; };
-        auto fetch = [&](int s) OCS_INLINE {
-          In v;
-          v.h = rec[RS * s];
-          v.hh = rec[RS * s + 1];
-          v.h6 = rec[RS * s + 2];
-          v.uM = us[(2 * s) * TPW];
-          v.uB = us[(2 * s + 1) * TPW];
-          return v;
-        };
-        In nxt = fetch(0);
-#pragma unroll
-        for (int s = 0; s < D; ++s) {
-          const In c = nxt;
-          if (s + 1 < D) nxt = fetch(s + 1);
-          __builtin_amdgcn_sched_barrier(0);
-          const double cM = P::row_vertex(mh, c.uM), cB = P::row_vertex(mh, c.uB);
-          const double F1 = P::row_f_shifted(y, cprev);
-          double Y = __builtin_fma(c.hh, F1, y);
-          w[s * SS] = double2{y, Y};                     // (Y1, Y2) - m/2
-          const double F2 = P::row_f_shifted(Y, cM);
-          Y = __builtin_fma(c.hh, F2, y);
-          const double Y3 = Y;
-          const double F3 = P::row_f_shifted(Y, cM);
-          Y = __builtin_fma(c.h, F3, y);
-          w[(D + s) * SS] = double2{Y3, Y};              // (Y3, Y4) - m/2
-          const double F4 = P::row_f_shifted(Y, cB);
-          y = __builtin_fma(c.h6, F4, __builtin_fma(c.h6, __builtin_fma(2.0, F3, __builtin_fma(2.0, F2, F1)), y));  // (F4 joins last:
-            // one dependent operation after it instead of two)
-          cprev = cB;
-          uprev = c.uB;
-        }
-      }
-      tc += PL_T() - t1;
-    }
-#ifdef OCS_PL_STAMPS
-    if (a.dbg && lane == 0) {
-      a.dbg[blockIdx.x * 16 + 4] = tb;
-      a.dbg[blockIdx.x * 16 + 5] = tc;
-    }
-#endif
-    (void)tb; (void)tc;
-    if (OUT_X && !fz) a.x[((size_t)a.N * NAUG + r) * B + b] = y + mh;  // x(t_N); the other nodes are stored by C
-  } else {
-    // ---------------- C: objective and the stores of the trajectory ----------------
-    // The G lanes of a trajectory take G consecutive steps (not the G rows of one step): a lane reads all rows of its
-    // step, so the sum over the rows needs no cross-lane reduction, the running objective is a prefix sum over the
-    // lanes of a quad, and every value is stored once.
-    //   d_i = W_A q1 + W_M (q2 + q3) + W_B q4,  q_j = sum_r row_q(Y_j,r), with the quadrature weights of the record
-    //   table (W_A = h/6 e^{-r t_A}, ...): the same sum as h/6 (F1 + 2 F2 + 2 F3 + F4) of the cost row.
-    const int csub = lane % G;
-    const int ctl = lane / G;
-    const int b = bw + ctl;
-    const uniform_ptr PS = as_uniform(a.ps);
-    typename P::RowPar rpr[G];
-    double mhr[G];
-#pragma unroll
-    for (int q = 0; q < G; ++q) {
-      rpr[q] = P::load_row([&](int k) OCS_INLINE {
-        return ((a.pmask >> k) & 1u) ? a.pb[(size_t)k * B + b] : PS[k];
-      }, q);
-      mhr[q] = P::row_shift(rpr[q]);
-    }
-    const bool fz = FRZ && a.frozen[b] != 0;
-    const size_t colB = (size_t)NAUG * B;
-    double carry = 0.0;  // running objective at the node before this lane's step (OUT_X) / this lane's share (else)
-    const bool wc = !fz && !a.nocost;  // the objective row is written
-    if (OUT_X && wc && csub == 0) a.x[(size_t)G * B + b] = 0.0;
-    long long tb = 0, tc = 0;
-    for (int k = 0; k <= nb; ++k) {
-      const long long t0 = PL_T();
-      lds_barrier();
-      const long long t1 = PL_T();
-      tb += t1 - t0;
-      if (k >= 1) {
-        const int j = k - 1;
-        const double* rec = &inp[j % NSLOT][0];
-        const double* us = rec + C_::REC_DBL + ctl;
-        const double2* st = &stage[j & 1][0][0][ctl * G];
-        const double ublk = ulast[j & 1][ctl * G];
-        // all LDS reads of the block first (the passes below then wait for their own only)
-        struct In { double wA, wM, wB, uA, uM, uB, Y[4][G]; };
-        In in[D / G];
-#pragma unroll
-        for (int p0 = 0; p0 < D; p0 += G) {
-          const int s = p0 + csub;
-          In& v = in[p0 / G];
-          v.wA = rec[RS * s + SCO + 3];
-          v.wM = rec[RS * s + SCO + 4];
-          v.wB = rec[RS * s + SCO + 5];
-          v.uM = us[(2 * s) * TPW];
-          v.uB = us[(2 * s + 1) * TPW];
-          v.uA = us[(s > 0 ? 2 * s - 1 : 0) * TPW];
-#pragma unroll
-          for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-            for (int q = 0; q < G; ++q) {
-              const double2 pr = st[(pp * D + s) * SS + q];
-              v.Y[2 * pp][q] = pr.x;
-              v.Y[2 * pp + 1][q] = pr.y;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int p0 = 0; p0 < D; p0 += G) {
-          const int s = p0 + csub;
-          const In& c = in[p0 / G];
-          const double uA = s > 0 ? c.uA : ublk;
-          const double uA2 = uA * uA, uM2 = c.uM * c.uM, uB2 = c.uB * c.uB;
-          double Y1[G];
-          const double cqM = P::control_q(uM2, rpr[0]);
-          double q1 = P::control_q(uA2, rpr[0]), q2 = cqM, q3 = cqM, q4 = P::control_q(uB2, rpr[0]);
-#pragma unroll
-          for (int q = 0; q < G; ++q) {
-            Y1[q] = c.Y[0][q] + mhr[q];
-            q1 = P::state_q_acc(Y1[q], q1);
-            q2 = P::state_q_acc(c.Y[1][q] + mhr[q], q2);
-            q3 = P::state_q_acc(c.Y[2][q] + mhr[q], q3);
-            q4 = P::state_q_acc(c.Y[3][q] + mhr[q], q4);
-          }
-          const double d = __builtin_fma(c.wA, q1, __builtin_fma(c.wM, q2 + q3, c.wB * q4));
-          if (OUT_X) {
-            // inclusive prefix over the G steps of the pass, on top of the running objective
-            double pre = d;
-            if (G >= 2) {
-              const double t = dpp_quad_pl<(G == 4) ? 0x90 : 0xA0>(pre);  // lane <- lane - 1
-              pre += (csub >= 1) ? t : 0.0;
-            }
-            if (G == 4) {
-              const double t = dpp_quad_pl<0x44>(pre);                    // lane <- lane - 2
-              pre += (csub >= 2) ? t : 0.0;
-            }
-            const double tot = carry + pre;
-            if (!fz) {
-              double* xn = a.x + (size_t)(j * D + s) * colB + b;  // node i = j D + s
-#pragma unroll
-              for (int q = 0; q < G; ++q) xn[(size_t)q * B] = Y1[q];
-              if (wc) xn[colB + (size_t)G * B] = tot;              // objective at node i + 1
-            }
-            carry = (G == 1) ? tot : dpp_quad_pl<(G == 4) ? 0xFF : 0xF5>(tot);  // the pass's last lane
-          } else {
-            carry += d;
-          }
-        }
-      }
-      tc += PL_T() - t1;
-    }
-#ifdef OCS_PL_STAMPS
-    if (a.dbg && lane == 0) {
-      a.dbg[blockIdx.x * 16 + 8] = tb;
-      a.dbg[blockIdx.x * 16 + 9] = tc;
-    }
-#endif
-    (void)tb; (void)tc;
-    const double Jt = OUT_X ? carry : group_sum_pl<G>(carry);
-    if (!fz) a.J[b] = Jt;
-  }
-}
 
 // ---------------------------------------------------------------------------------------
 // backward.  Blocks are numbered from the END of the horizon: block j covers steps
@@ -548,7 +104,6 @@ struct BwdArgsPL {
   double* lam;   // state rows by the adjoint wave A, the constant cost row by R
   double* dJdu;
   double* lam0;
-  long long* dbg;  // diagnostic build only
   const double* pend0;  // optional [B]: the k1 half of the last column (2N) when the steps above N were done by
                         // another kernel (a pass split at a multiple of the block length); default 0
 };
@@ -558,7 +113,7 @@ template <class P, bool OUT_LAM, bool OUT_DJDU, bool LT>
 __global__ __launch_bounds__(256) void k_backward_pl(const BwdArgsPL a) {
   constexpr int G = P::NS, NAUG = P::NAUG;
   static_assert(P::NC == 1 && P::NTC == 1, "pipeline kernels are written for one control and one time coefficient");
-  using C_ = PLCfg<G, true>;
+  using C_ = PLCfg<G>;
   constexpr int D = C_::D, TPW = C_::TPW, Q = C_::Q, NSLOT = C_::NSLOT, RS = C_::RS, SCO = C_::SCO;
   constexpr int UOFF = C_::REC_DBL, XOFF = C_::REC_DBL + C_::U_DBL;
   // R -> A: the four stage states as two 16-byte pairs (Y1, Y2), (Y3, Y4): two LDS instructions on either side
@@ -622,12 +177,8 @@ __global__ __launch_bounds__(256) void k_backward_pl(const BwdArgsPL a) {
     const double lamc2 = a.lamT ? a.lamT[(size_t)G * B + bw + tl2] : 1.0;
     double* lc = a.lam + (size_t)G * B + bw + tl2;
     if (OUT_LAM && so == 0) lc[(size_t)N * colB] = lamc2;
-    long long tb = 0, tc = 0;
     for (int k = 0; k <= nb + 1; ++k) {
-      const long long t0 = PL_T();
       lds_barrier();
-      const long long t1 = PL_T();
-      tb += t1 - t0;
       if (OUT_LAM && k < nb) {
         const int itop = N - 1 - k * D;
 #pragma unroll
@@ -665,25 +216,13 @@ __global__ __launch_bounds__(256) void k_backward_pl(const BwdArgsPL a) {
           w[(1 * D + s) * 64] = double2{Y3, Y4};
         }
       }
-      tc += PL_T() - t1;
     }
-#ifdef OCS_PL_STAMPS
-    if (a.dbg && lane == 0) {
-      a.dbg[blockIdx.x * 16 + 0] = tb;
-      a.dbg[blockIdx.x * 16 + 1] = tc;
-    }
-#endif
-    (void)tb; (void)tc;
   } else if (wave == 2) {
     // ---------------- A: adjoint recursion ----------------
     double lam = a.lamT ? a.lamT[(size_t)r * B + b] : 0.0;
     if (OUT_LAM) a.lam[(size_t)N * colB + (size_t)r * B + b] = lam;
-    long long tb = 0, tc = 0;
     for (int k = 0; k <= nb + 1; ++k) {
-      const long long t0 = PL_T();
       lds_barrier();
-      const long long t1 = PL_T();
-      tb += t1 - t0;
       if (k >= 1 && k <= nb) {
         const int j = k - 1;
         const double* slot = &inp[j % NSLOT][0];
@@ -735,15 +274,7 @@ __global__ __launch_bounds__(256) void k_backward_pl(const BwdArgsPL a) {
           if (OUT_LAM) kw[(3 * D + s) * KS] = lam;  // stored by D
         }
       }
-      tc += PL_T() - t1;
     }
-#ifdef OCS_PL_STAMPS
-    if (a.dbg && lane == 0) {
-      a.dbg[blockIdx.x * 16 + 4] = tb;
-      a.dbg[blockIdx.x * 16 + 5] = tc;
-    }
-#endif
-    (void)tb; (void)tc;
     if (a.lam0) {
       a.lam0[(size_t)r * B + b] = lam;
       a.lam0[(size_t)G * B + b] = lamc;
@@ -766,12 +297,8 @@ __global__ __launch_bounds__(256) void k_backward_pl(const BwdArgsPL a) {
     // carried from pass to pass by the lane of the last (lowest) step: its B'k1 and its node control
     double pend = a.pend0 ? a.pend0[bx] : 0.0;
     double ucar = OUT_DJDU ? a.u[(size_t)(2 * N) * B + bx] : 0.0;
-    long long tb = 0, tc = 0;
     for (int k = 0; k <= nb + 1; ++k) {
-      const long long t0 = PL_T();
       lds_barrier();
-      const long long t1 = PL_T();
-      tb += t1 - t0;
       if (k >= 2) {
         const int j = k - 2;
         const double* slot = &inp[j % NSLOT][0];
@@ -838,15 +365,7 @@ __global__ __launch_bounds__(256) void k_backward_pl(const BwdArgsPL a) {
           }
         }
       }
-      tc += PL_T() - t1;
     }
-#ifdef OCS_PL_STAMPS
-    if (a.dbg && lane == 0) {
-      a.dbg[blockIdx.x * 16 + 8] = tb;
-      a.dbg[blockIdx.x * 16 + 9] = tc;
-    }
-#endif
-    (void)tb; (void)tc;
     if (OUT_DJDU && csub == 0) a.dJdu[bx] = pend;  // left end point :101-102
   }
 }
@@ -872,7 +391,7 @@ struct CostateCfg {
   static constexpr int LPB = NREC + 2 * NX;
 };
 struct CostateArgsPL {
-  int N, batch, ld;       // ld: row distance of the arrays (window of a larger batch) or 0
+  int N, batch;
   const double* REC;
   const double* ps;
   const double* pb;
@@ -895,7 +414,7 @@ __global__ __launch_bounds__(128) void k_costate_pl(const CostateArgsPL a) {
   __shared__ __attribute__((aligned(16))) double inp[NSLOT][C_::SLOT];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const size_t B = (size_t)(a.ld ? a.ld : a.batch);
+  const size_t B = (size_t)a.batch;
   const int N = a.N, nb = N / D;
   const int bw = tile_base(blockIdx.x, TPW, a.batch);
   if (wave == 0) {
@@ -1106,7 +625,7 @@ __global__ __launch_bounds__(MET ? 576 : 320) void k_costate_plx(const CostateXA
   __shared__ double xres[MET ? 3 : 1][3][64];                   // MET: the partial maxima of the X waves
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const size_t B = (size_t)(a.ld ? a.ld : a.batch);
+  const size_t B = (size_t)a.batch;
   const int N = a.N, nb = N / D;
   const int bw = tile_base(blockIdx.x, TPW, a.batch);
   if (aa.gate && *aa.gate == 0) return;
@@ -1321,11 +840,11 @@ int costate_prec() { return kPRec; }
 bool costate_pl_ok(Functor f, int nS, int nC, int N, int batch);
 // PR: [N][costate_prec()] interval records; the midpoints are formed inside (no xmid array)
 int launch_costate_plx(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* PR,
-                       const int* frozen, double* dump, double* lam, int ld, hipStream_t s, const int* gate) {
+                       const int* frozen, double* dump, double* lam, hipStream_t s, const int* gate) {
   if (!costate_pl_ok(p.functor, p.nS, p.nC, g.N, batch) || (frozen && !dump) || !PR) return -1;
-  if (ld == 0 && costate_scan_ok(p, g, batch)) return launch_costate_scan(p, g, batch, x, ldx, PR, frozen, lam, s, gate);
+  if (costate_scan_ok(p, g, batch)) return launch_costate_scan(p, g, batch, x, ldx, PR, frozen, lam, s, gate);
   CostateXArgs a{};   // (the MET fields stay zero: the plain costate pass)
-  a.c = CostateArgsPL{g.N, batch, ld, g.REC, p.ps, p.pb, p.pmask, x, ldx, nullptr, frozen, dump, lam};
+  a.c = CostateArgsPL{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, nullptr, frozen, dump, lam};
   a.PR = PR;
   a.gate = gate;
   if (p.nS == 1)
@@ -1348,7 +867,7 @@ int launch_costate_met(const ProblemDesc& p, const GridDesc& g, int batch, const
   if (!costate_pl_ok(p.functor, p.nS, p.nC, g.N, batch) || !PR || !g.TU || !status || !maxChange || !nactive) return -1;
   if (costate_scan_ok(p, g, batch))
     return launch_costate_scan_met(p, g, batch, x, ldx, PR, lb, ub, relTol, absTol, sweep, status, maxChange, nactive, lam, s, gate);
-  const CostateXArgs a{CostateArgsPL{g.N, batch, 0, g.REC, p.ps, p.pb, p.pmask, x, ldx, nullptr, status, nullptr, lam},
+  const CostateXArgs a{CostateArgsPL{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, nullptr, status, nullptr, lam},
                        PR, gate, g.TU, lb, ub, relTol, absTol, sweep, status, maxChange, nactive};
   const dim3 grid(tile_count(batch, 64 / p.nS)), block(576);
   if (p.nS == 1)
@@ -1377,9 +896,9 @@ static void run_costate_pl(const CostateArgsPL& a, hipStream_t s) {
     k_costate_pl<P, false><<<grid, block, 0, s>>>(a);
 }
 int launch_costate_pl(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* xmid,
-                      const int* frozen, double* dump, double* lam, int ld, hipStream_t s) {
+                      const int* frozen, double* dump, double* lam, hipStream_t s) {
   if (!costate_pl_ok(p.functor, p.nS, p.nC, g.N, batch) || (frozen && !dump)) return -1;
-  const CostateArgsPL a{g.N, batch, ld, g.REC, p.ps, p.pb, p.pmask, x, ldx, xmid, frozen, dump, lam};
+  const CostateArgsPL a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, xmid, frozen, dump, lam};
   if (p.nS == 1)
     run_costate_pl<LogisticK<1>>(a, s);
   else if (p.nS == 2)
@@ -1399,66 +918,10 @@ bool pipeline_shape_ok(int nS, int N, int batch, bool backward) {
   const int D = 8, TPW = 64 / nS;
   if (N < D || N % D != 0) return false;
   // whole tiles; the state pass (k_forward_p2) also takes a ragged last tile as a workgroup that overlaps its neighbour, given
-  // at least one tile and an even row distance (ocs_pipeline2_kernel.hpp)
+  // at least one tile and an even batch (ocs_pipeline2_kernel.hpp)
   return batch % TPW == 0 || (!backward && tile_ok(batch, TPW));
 }
 int pipeline_block_steps() { return 8; }
-
-template <class P>
-static void run_forward_pl(const FwdArgsPL& a, hipStream_t s) {
-  constexpr int TPW = 64 / P::NS;
-  const dim3 grid(a.batch / TPW), block(192);
-  if (a.frozen) {
-    if (a.x)
-      k_forward_pl<P, true, true><<<grid, block, 0, s>>>(a);
-    else
-      k_forward_pl<P, false, true><<<grid, block, 0, s>>>(a);
-  } else if (a.x) {
-    k_forward_pl<P, true, false><<<grid, block, 0, s>>>(a);
-  } else {
-    k_forward_pl<P, false, false><<<grid, block, 0, s>>>(a);
-  }
-}
-int launch_forward_pl(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
-                      double* x, double* J, const int* frozen, double* dump, int ld, hipStream_t s,
-                      bool no_cost_row, const int* gate) {
-  if (!pipeline_shape_ok(p.nS, g.N, batch, false) || (frozen && !dump)) return -1;
-  static const bool v1 = getenv("OCS_FWD_V1") != nullptr;   // the previous kernel, for A/B timing
-  if (!v1) return launch_forward_p2(p, g, batch, x0, u, x, J, frozen, ld, s, no_cost_row, gate);
-  if (batch % (64 / p.nS) != 0) return -1;   // (the previous kernel: whole tiles only)
-  FwdArgsPL a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, nullptr, frozen, dump, ld, no_cost_row ? 1 : 0, gate};
-#ifdef OCS_PL_STAMPS
-  static long long* dbg = nullptr;
-  const int nwg = batch / (64 / p.nS);
-  if (!dbg) (void)hipMalloc((void**)&dbg, sizeof(long long) * 16 * 65536);
-  (void)hipMemsetAsync(dbg, 0, sizeof(long long) * 16 * nwg, s);
-  a.dbg = dbg;
-#endif
-  if (p.nS == 1)
-    run_forward_pl<LogisticK<1>>(a, s);
-  else if (p.nS == 2)
-    run_forward_pl<LogisticK<2>>(a, s);
-  else if (p.nS == 4)
-    run_forward_pl<LogisticK<4>>(a, s);
-  else
-    return -1;
-#ifdef OCS_PL_STAMPS
-  {
-    (void)hipStreamSynchronize(s);
-    static int calls = 0;
-    if (++calls % 8 == 0) {
-      std::vector<long long> h(16 * nwg);
-      (void)hipMemcpy(h.data(), dbg, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
-      double acc[16] = {0};
-      for (int w = 0; w < nwg; ++w)
-        for (int q = 0; q < 16; ++q) acc[q] += (double)h[16 * w + q] / nwg;
-      fprintf(stderr, "[pl fwd nS=%d] cycles per wg: M wait %.0f barrier %.0f total %.0f | S barrier %.0f compute %.0f | C barrier %.0f compute %.0f\n",
-              p.nS, acc[0], acc[1], acc[2], acc[4], acc[5], acc[8], acc[9]);
-    }
-  }
-#endif
-  return hip_rc5(hipGetLastError());
-}
 
 template <class P>
 static void run_backward_pl(const BwdArgsPL& a, hipStream_t s) {
@@ -1483,14 +946,7 @@ int launch_backward_pl(const ProblemDesc& p, const GridDesc& g, int batch, const
                        const double* lamT, double* lam, double* dJdu, double* lam0, const double* pend0,
                        hipStream_t s) {
   if (!pipeline_shape_ok(p.nS, g.N, batch, true) || (!lam && !dJdu)) return -1;
-  BwdArgsPL a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, xck, u, lamT, lam, dJdu, lam0, nullptr, pend0};
-#ifdef OCS_PL_STAMPS
-  static long long* dbgb = nullptr;
-  const int nwg = batch / (64 / p.nS);
-  if (!dbgb) (void)hipMalloc((void**)&dbgb, sizeof(long long) * 16 * 65536);
-  (void)hipMemsetAsync(dbgb, 0, sizeof(long long) * 16 * nwg, s);
-  a.dbg = dbgb;
-#endif
+  BwdArgsPL a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, xck, u, lamT, lam, dJdu, lam0, pend0};
   if (p.nS == 1)
     run_backward_pl<LogisticK<1>>(a, s);
   else if (p.nS == 2)
@@ -1499,21 +955,6 @@ int launch_backward_pl(const ProblemDesc& p, const GridDesc& g, int batch, const
     run_backward_pl<LogisticK<4>>(a, s);
   else
     return -1;
-#ifdef OCS_PL_STAMPS
-  {
-    (void)hipStreamSynchronize(s);
-    static int calls = 0;
-    if (++calls % 8 == 0) {
-      std::vector<long long> h(16 * nwg);
-      (void)hipMemcpy(h.data(), dbgb, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
-      double acc[16] = {0};
-      for (int w = 0; w < nwg; ++w)
-        for (int q = 0; q < 16; ++q) acc[q] += (double)h[16 * w + q] / nwg;
-      fprintf(stderr, "[pl bwd nS=%d] cycles per wg: R barrier %.0f compute %.0f | A barrier %.0f compute %.0f | D barrier %.0f compute %.0f\n",
-              p.nS, acc[0], acc[1], acc[4], acc[5], acc[8], acc[9]);
-    }
-  }
-#endif
   return hip_rc5(hipGetLastError());
 }
 

@@ -64,8 +64,6 @@ struct FwdArgs {
   double* dump;         //   a converged instance keeps the x, J of the sweep it converged in); its stores go to dump[b]
   const double* yc0;    // optional [B]: running objective at the first node (a pass continued from another
                         //               kernel's last column; default 0, RK4Integrator.m:33)
-  int ld;               // distance between rows of the batch-minor arrays when it is not `batch` (a launch on a
-                        // window of a larger batch: pointers are offset, `batch` counts the window); 0 = batch
   const int* gate = nullptr;   // optional: the launch does nothing if *gate == 0 (a sweep of fb_sweep enqueued before the
                                // host knew that the sweep before it had left no instance active)
 };
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(64) void k_forward(const FwdArgs a) {
   using Rec = StepRec<NTC>;
   const int b0 = blockIdx.x * 64 + threadIdx.x;
   const int b = b0 < a.batch ? b0 : a.batch - 1;
-  const size_t B = (size_t)(a.ld ? a.ld : a.batch);
+  const size_t B = (size_t)a.batch;
   const int N = a.N;
   const uniform_ptr PS = as_uniform(a.ps);
   const double* REC = a.REC;

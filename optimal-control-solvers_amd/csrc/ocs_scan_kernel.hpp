@@ -144,8 +144,7 @@ constexpr int kScanPadBack = 8;    // and after step N-1 (a wave copies 8 record
 constexpr bool kScanXRC = OCS_SCAN_XRC != 0;
 
 // W waves per workgroup (chunks per superblock), L steps per chunk
-// ABL (diagnostic builds, -DOCS_SCAN_ABL): 1 no stores, 2 no phase 3, 3 no phase 1, 4 no loads, 5 no barrier/phase 2
-template <class P, int W, int L, bool OUT_LAM, bool OUT_DJDU, bool LT, int ABL = 0>
+template <class P, int W, int L, bool OUT_LAM, bool OUT_DJDU, bool LT>
 __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
   constexpr int G = P::NS, NAUG = P::NAUG, TPW = 64 / G;
   static_assert(P::NC == 1 && P::NTC == 1 && P::ROW_SEPARABLE, "scan kernels: row-separable problems, one control");
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
     //  from the front pad: identity maps)
     const int lr = lo >= 0 ? lo - 1 : -kScanPadFront;
     if (q == 0) dma16_sc(a.RECS + (long long)lr * kScanRec + 2 * lane, &rcs[slot][wave][0]);
-    const Buf bx = Buf::make(a.xck + (size_t)lc * colB, ABL == 4 ? 0 : kNumRec), bu = Buf::make(a.u + (size_t)(2 * lc) * B, ABL == 4 ? 0 : kNumRec);
+    const Buf bx = Buf::make(a.xck + (size_t)lc * colB), bu = Buf::make(a.u + (size_t)(2 * lc) * B);
     if (!kScanXRC || q == 0) d.x[q] = bx.ld(vx, (unsigned)q * col8);
     d.u[2 * q] = bu.ld(vu, (unsigned)(2 * q) * B8);
     d.u[2 * q + 1] = bu.ld(vu, (unsigned)(2 * q + 1) * B8);
@@ -248,7 +247,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
     xs[0] = d.x[0];
     double A = 1.0, Bq = 0.0;
 #pragma unroll
-    for (int q = 0; q < L && ABL != 3; ++q) {
+    for (int q = 0; q < L; ++q) {
       const Rc c = rec_of(rw, q);
       const double xi = xs[q], uA = d.u[2 * q], uM = d.u[2 * q + 1], uB = d.u[2 * q + 2];
       const double F1 = P::g_row_f(xi, uA, c.tA, rp);           // compute_states :39-46, this row
@@ -288,12 +287,8 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
       load_part(sb + 1, dn, slot ^ 1, q);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (ABL == 3) {
-#pragma unroll
-      for (int q = 1; q < L; ++q) xs[q] = xs[0];
-    }
     sm[sb & 1][wave][lane] = double2{A, Bq};
-    if (ABL != 5) lds_barrier_sc();
+    lds_barrier_sc();
     // ---------------- phase 2: lam at the top of this chunk ----------------
     // lam at the top of the superblock: lamT for the first one, afterwards what the LAST wave of the previous
     // superblock left at the bottom of its chunk (published to LDS behind its phase 3, i.e. before this superblock's
@@ -301,7 +296,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
     // would hold 4 W registers), and superblock boundaries carry the serial recursion's own value.
     double lam = (sb == 0) ? carry : csm[(sb & 1) ^ 1][lane];
 #pragma unroll
-    for (int j0 = 0; j0 < W && ABL != 5; j0 += 4) {
+    for (int j0 = 0; j0 < W; j0 += 4) {
       if (j0 < wave) {   // wave-uniform
         double2 ab[4];
 #pragma unroll
@@ -316,7 +311,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
       }
     }
     // ---------------- phase 3: the recursion inside the chunk, lam and dJdu stores ----------------
-    const int lc = live ? lo : 0, nrec = (live && ABL != 1) ? kNumRec : 0;   // a dead chunk stores nothing
+    const int lc = live ? lo : 0, nrec = live ? kNumRec : 0;   // a dead chunk stores nothing
     const Buf bl = Buf::make(a.lam + (size_t)lc * colB, nrec), bd = Buf::make(a.dJdu + (size_t)(2 * lc) * B, nrec);
     if (OUT_LAM) {
       // the constant cost row of lam for the L columns of the chunk
@@ -324,9 +319,8 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
       for (int q0 = 0; q0 < L; q0 += G) bl.st(lamc, vc, (unsigned)q0 * col8);
     }
     double pend = topc ? pend_top : 0.0;   // this row's B'k1 share of the node above
-    if (ABL == 2) lam += xs[0] + d.u[0];
 #pragma unroll
-    for (int q = L - 1; q >= 0 && ABL != 2; --q) {
+    for (int q = L - 1; q >= 0; --q) {
       const Rc c = rec_of(rw, q);
       // the stage states again (held registers are worth more than these nine operations: 4 waves per SIMD)
       const double xi = xs[q], uA = d.u[2 * q], uM = d.u[2 * q + 1], uB = d.u[2 * q + 2];

@@ -58,14 +58,6 @@ static void run_backward_scan(const BwdArgsScan& a, hipStream_t s) {
     else
       k_backward_scan<P, kScanW, kScanL, false, true, true><<<grid, block, 0, s>>>(a);
   } else if (a.lam && a.dJdu) {
-#ifdef OCS_SCAN_ABL
-    static const int abl = getenv("OCS_SCAN_ABL") ? atoi(getenv("OCS_SCAN_ABL")) : 0;
-    if (abl == 1) return (void)(k_backward_scan<P, kScanW, kScanL, true, true, false, 1><<<grid, block, 0, s>>>(a));
-    if (abl == 2) return (void)(k_backward_scan<P, kScanW, kScanL, true, true, false, 2><<<grid, block, 0, s>>>(a));
-    if (abl == 3) return (void)(k_backward_scan<P, kScanW, kScanL, true, true, false, 3><<<grid, block, 0, s>>>(a));
-    if (abl == 4) return (void)(k_backward_scan<P, kScanW, kScanL, true, true, false, 4><<<grid, block, 0, s>>>(a));
-    if (abl == 5) return (void)(k_backward_scan<P, kScanW, kScanL, true, true, false, 5><<<grid, block, 0, s>>>(a));
-#endif
     k_backward_scan<P, kScanW, kScanL, true, true, false><<<grid, block, 0, s>>>(a);
   } else if (a.lam) {
     k_backward_scan<P, kScanW, kScanL, true, false, false><<<grid, block, 0, s>>>(a);

@@ -121,7 +121,8 @@ def fb_sweep_batch(prob, x0, tspan, options=None, integrator=None):
 
 def fb_sweep_path(integrator):
     """Diagnostic (ocs.h ocs_fb_sweep_path): the sweep loop the last fb_sweep on this integrator ran -- 1 kernel by kernel
-    as the reference sequences it, 2 fused control update, 3 windows, 4 the two-kernel sweep (fold)."""
+    as the reference sequences it, 2 fused control update, 4 the two-kernel sweep (fold), 5 the sequence of 1 with the error
+    points off the grid nodes, enqueued ahead."""
     return int(lib.ocs_fb_sweep_path(integrator._h))
 
 

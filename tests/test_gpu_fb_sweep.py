@@ -151,16 +151,12 @@ def test_fused_costate_update_equals_separate_kernels(ocs, oracle, nS, N, batch)
     ra = ocs.fb_sweep_batch(prob, x0, tspan, dict(base))
     rb = ocs.fb_sweep_batch(prob, x0, tspan, dict(base, fused_update_off=1))
     if batch >= 128:
-        # the same with the batch cut into windows that run their sweep loops on separate streams: an instance's
-        # result does not depend on which window it is in
+        # nWINDOWS is ignored (kept for the layout of ocs_fbs_options): the result is the default run's, bit for bit
         rw = ocs.fb_sweep_batch(prob, x0, tspan, dict(base, nWINDOWS=2))
         assert np.array_equal(ra["sweeps"], rw["sweeps"])
-        # (a ragged last window runs the lane kernel: another order of the objective sum, and the plain form of the
-        # logistic rows where the pipeline kernel marches about their vertex -- round-off level differences)
         for key in ("x", "lam", "u", "J"):
-            assert relerr(ra[key], rw[key]) < 1e-12, key
-        assert relerr(np.nan_to_num(ra["maxChange"]), np.nan_to_num(rw["maxChange"])) < 1e-6
-        assert np.array_equal(np.isnan(ra["maxChange"]), np.isnan(rw["maxChange"]))
+            assert np.array_equal(ra[key], rw[key]), key
+        assert np.array_equal(ra["maxChange"], rw["maxChange"], equal_nan=True)
     # ... without the fold of the control update into the state pass of the next sweep (option 3: sweeps >= 2 are
     # forward, costate, control update, advance instead of forward-with-ControlChar, costate-with-convergence-test)
     rd = ocs.fb_sweep_batch(prob, x0, tspan, dict(base, fused_update_off=3))
