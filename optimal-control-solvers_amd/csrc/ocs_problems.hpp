@@ -184,6 +184,10 @@ struct LogisticK {
     (void)y;
     return row_dfdu(rp.cw * u, v, st.ev);
   }
+  // the same row as g_row_dfdu_v v + g_row_dfdu_0 (the coefficient of v reads neither y nor u, the rest does not read
+  // y): a scan that has v as an affine function of lam carries the result as one too (k_backward_scan)
+  __device__ static inline double g_row_dfdu_v(const Stage& st, const RowPar& rp) { (void)st; (void)rp; return -1.0; }
+  __device__ static inline double g_row_dfdu_0(double u, const Stage& st, const RowPar& rp) { return (rp.cw * u) * st.ev; }
 
   // Gen-1 ControlChar through the A9 adapter (make_from_symbolic.m:19-23,111):
   //   dHdu = -sum(lam) + 2 c e^{-rt} u = 0  ->  u = sum(lam) e^{rt} / (2c), clamped to the bounds.

@@ -16,10 +16,14 @@
 //   phase 2  (W-term scan)    the W chunk maps of a superblock (W chunks = W L steps) go through LDS; every
 //            wave composes them in time order on top of the carry (lam at the top of the superblock), which
 //            gives it lam at the top of its own chunk and the next carry.  One LDS barrier per superblock.
-//   phase 3  (time-parallel)  with the true lam at the top of its chunk a wave runs lines :73-88 exactly as the
-//            reference writes them (stage states recomputed once more; inside a chunk the arithmetic is the
-//            serial kernels'), stores lam and
-//            assembles the dJdu columns (:97-121).
+//   phase 3  (time-parallel)  with the true lam at the top of its chunk a wave walks down its L steps, stores lam and
+//            assembles the dJdu columns (:97-121).  Where (dF/du)'v does not read y (!P::DFDU_READS_Y: the registry
+//            problems) everything a step stores is affine in lam_{i+1} as well -- lam_i, and this row's shares of the
+//            midpoint column (B'k2 + B'k3) and of the two node columns (B'k1, B'k4) -- and phase 1 keeps those
+//            coefficients in registers in place of the stage states: a step of phase 3 is four FMAs and the row sums,
+//            with no stage state and no row function.  For the other problems (user problems given as row functions,
+//            ocs_user_functor.hpp) phase 3 forms the stage states once more and runs :73-88 as the reference writes
+//            them (inside a chunk the arithmetic is the serial kernels').
 //
 // Superblocks are taken from the end of the horizon; the loads of superblock k+1 are issued before superblock k
 // is processed (two register sets), so HBM latency lies under a whole superblock of arithmetic and the pass
@@ -27,8 +31,10 @@
 // and two dJdu columns.  Steps below 0 in the last superblock run as exact identity maps (records with
 // h = 0 on clamped inputs), so any N works; stores are predicated, so any batch works.
 //
-// Differences to the serial kernels: lam at the chunk boundaries comes from composed maps, i.e. a different
-// association of the same products and sums (round-off level; tolerance 1e-12 as for the other mappings).
+// Differences to the serial kernels: lam at the chunk boundaries comes from composed maps, and (registry problems) lam
+// and dJdu inside a chunk from the per-step affine forms, i.e. a different association of the same products and sums
+// (round-off level; tolerance 1e-12 as for the other mappings).  The lam-only, dJdu-only and combined instances share
+// one arithmetic path and store the same bits.
 // The composed products prod(alpha) must stay inside the fp64 range.
 // This header holds the kernel template only (it is also compiled by hipRTC for user problems given as row functions,
 // csrc/ocs_user_functor.hpp); the launchers are in ocs_scan_kernels.hip.  Functor interface: the g_* names of
@@ -150,6 +156,9 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
   static_assert(P::NC == 1 && P::NTC == 1 && P::ROW_SEPARABLE, "scan kernels: row-separable problems, one control");
   static_assert(L % G == 0 && W * L + 1 <= kScanPadFront && L + 1 <= 8, "chunk shape");
   typedef typename P::Stage Stage;
+  // phase 3 from phase 1's affine step records where (dF/du)'v does not read y (registry problems); user problems
+  // given as row functions (DFDU_READS_Y) form the stage states again
+  constexpr bool AFF = !P::DFDU_READS_Y;
   __shared__ __attribute__((aligned(16))) double2 sm[2][W][64];      // chunk maps
   __shared__ double csm[2][64];                                      // lam at the bottom of a superblock
   __shared__ __attribute__((aligned(16))) double rcs[2][W][8 * kScanRec];   // records lo-1 .. lo+6 of a wave's chunk (1 KiB)
@@ -246,6 +255,12 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
     double xs[L];
     xs[0] = d.x[0];
     double A = 1.0, Bq = 0.0;
+    // AFF: what phase 3 needs of step i = lo + q, as affine functions of lam_{i+1}, kept instead of the stage states:
+    // lam_i (al, be), the midpoint column p23 (mp, mq), the k1 half of node column 2i (c1 kp, kq_i) and the k4 half of
+    // node column 2i+2 (c4 h6, fq_i), with c v + d = (dF/du)'v of a stage (g_row_dfdu_v, g_row_dfdu_0); c1 and c4 read
+    // the record only and are applied in phase 3.  The constants of a node column are kept as one: nq[q] = fq_i +
+    // kq_{i+1} (q < L-1), nq[L-1] = fq of the top step, nb = kq_lo + the constant of the k4 half of step lo-1.
+    double al[L], be[L], mp[L], mq[L], kp[L], nq[L], nb = 0.0;
 #pragma unroll
     for (int q = 0; q < L; ++q) {
       const Rc c = rec_of(rw, q);
@@ -283,6 +298,29 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
       const double beta = ((g1q + g2q) + g3q) + g0q;
       Bq = __builtin_fma(A, beta, Bq);
       A = A * alpha;
+      if constexpr (AFF) {
+        al[q] = alpha;
+        be[q] = beta;
+        if (OUT_DJDU) {   // (dF/du)'v = c v + d per stage; stages 2 and 3 share u and the stage values  :97-121
+          const double c3 = P::g_row_dfdu_v(s3, rp), d3 = P::g_row_dfdu_0(uM, s3, rp), c1 = P::g_row_dfdu_v(s1, rp);
+          mp[q] = c3 * k3p + c3 * k2p;
+          mq[q] = __builtin_fma(c3, k3q, d3) + __builtin_fma(c3, k2q, d3);
+          kp[q] = k1p;
+          const double kq = __builtin_fma(c1, k1q, P::g_row_dfdu_0(uA, s1, rp));
+          if (q == 0) {
+            const Rc cb = rec_of(rw, -1);
+            nb = kq + P::g_row_dfdu_0(uA, P::template stage<LT>(cb.s4, cb.h6, cb.tB, lamc), rp);
+          } else {
+            nq[q - 1] += kq;
+          }
+          nq[q] = P::g_row_dfdu_0(uB, s4, rp);
+          // formed here, not sunk below the barrier (that would keep u, the stage values and the k pairs alive instead)
+          asm volatile("" : "+v"(mp[q]), "+v"(mq[q]), "+v"(kp[q]));
+          if (q == 0) asm volatile("" : "+v"(nb));
+          if (q > 0) asm volatile("" : "+v"(nq[q - 1]));
+          if (q == L - 1) asm volatile("" : "+v"(nq[q]));
+        }
+      }
       __builtin_amdgcn_sched_barrier(0);   // one step at a time: the temporaries of interleaved steps cost occupancy
       load_part(sb + 1, dn, slot ^ 1, q);
       __builtin_amdgcn_sched_barrier(0);
@@ -319,61 +357,92 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
       for (int q0 = 0; q0 < L; q0 += G) bl.st(lamc, vc, (unsigned)q0 * col8);
     }
     double pend = topc ? pend_top : 0.0;   // this row's B'k1 share of the node above
+    double lt2 = 0.0;                        // (AFF) lam_{i+2}
 #pragma unroll
     for (int q = L - 1; q >= 0; --q) {
-      const Rc c = rec_of(rw, q);
-      // the stage states again (held registers are worth more than these nine operations: 4 waves per SIMD)
-      const double xi = xs[q], uA = d.u[2 * q], uM = d.u[2 * q + 1], uB = d.u[2 * q + 2];
-      double f = P::g_row_f(xi, uA, c.tA, rp);
-      const double Y2 = __builtin_fma(c.hh, f, xi);
-      f = P::g_row_f(Y2, uM, c.tM, rp);
-      const double Y3 = __builtin_fma(c.hh, f, xi);
-      f = P::g_row_f(Y3, uM, c.tM, rp);
-      const double Y4 = __builtin_fma(c.h, f, xi);
-      const Stage s4 = P::template stage<LT>(c.s4, c.h6, c.tB, lamc), s3 = P::template stage<LT>(c.s3, c.h3, c.tM, lamc),
-                  s1 = P::template stage<LT>(c.s1, c.h6, c.tA, lamc);
-      const double h6l = c.h6 * lam, h3l = c.h3 * lam;
-      const double k4 = h6l;                                     // :73
-      const double g3 = P::g_row_dfdx(Y4, uB, k4, s4, rp);       // :74-75
-      const double k3 = __builtin_fma(c.h, g3, h3l);             // :77
-      const double g2 = P::g_row_dfdx(Y3, uM, k3, s3, rp);       // :78-79
-      const double k2 = __builtin_fma(c.hh, g2, h3l);            // :81
-      const double g1 = P::g_row_dfdx(Y2, uM, k2, s3, rp);       // :82-83
-      const double k1 = __builtin_fma(c.hh, g1, h6l);            // :85
-      const double g0 = P::g_row_dfdx(xi, uA, k1, s1, rp);       // :87-88
-      lam = (((lam + g1) + g2) + g3) + g0;                       // :86-88
+      // lam_i and this row's shares of column 2i+1 (p23), column 2i+2 (pn) and, q = 0, column 2 lo (pb)   :73-121
+      double p23 = 0.0, pn = 0.0, pb = 0.0;
+      if constexpr (AFF) {
+        const double lt = lam;                                   // lam_{i+1}
+        lam = __builtin_fma(al[q], lt, be[q]);
+        if (OUT_DJDU) {
+          // c of the stage-4 half of step lo + j, times h6 (k4 = h6 lam), and of the stage-1 half
+          auto c4h6 = [&](int j) OCS_INLINE {
+            const Rc r = rec_of(rw, j);
+            return P::g_row_dfdu_v(P::template stage<LT>(r.s4, r.h6, r.tB, lamc), rp) * r.h6;
+          };
+          auto c1 = [&](int j) OCS_INLINE {
+            const Rc r = rec_of(rw, j);
+            return P::g_row_dfdu_v(P::template stage<LT>(r.s1, r.h6, r.tA, lamc), rp);
+          };
+          p23 = __builtin_fma(mp[q], lt, mq[q]);
+          pn = __builtin_fma(c4h6(q), lt, nq[q]);
+          if (q == L - 1)
+            pn = pend + pn;
+          else
+            pn = __builtin_fma(c1(q + 1) * kp[q + 1], lt2, pn);
+          if (q == 0)   // column 2 lo: the k1 half of step lo, the k4 half of step lo-1 (k4 = h/6 lam_lo)
+            pb = __builtin_fma(c4h6(-1), lam, __builtin_fma(c1(0) * kp[0], lt, nb));
+          lt2 = lt;
+        }
+      } else {
+        const Rc c = rec_of(rw, q);
+        // the stage states again (held registers are worth more than these nine operations: 4 waves per SIMD)
+        const double xi = xs[q], uA = d.u[2 * q], uM = d.u[2 * q + 1], uB = d.u[2 * q + 2];
+        double f = P::g_row_f(xi, uA, c.tA, rp);
+        const double Y2 = __builtin_fma(c.hh, f, xi);
+        f = P::g_row_f(Y2, uM, c.tM, rp);
+        const double Y3 = __builtin_fma(c.hh, f, xi);
+        f = P::g_row_f(Y3, uM, c.tM, rp);
+        const double Y4 = __builtin_fma(c.h, f, xi);
+        const Stage s4 = P::template stage<LT>(c.s4, c.h6, c.tB, lamc), s3 = P::template stage<LT>(c.s3, c.h3, c.tM, lamc),
+                    s1 = P::template stage<LT>(c.s1, c.h6, c.tA, lamc);
+        const double h6l = c.h6 * lam, h3l = c.h3 * lam;
+        const double k4 = h6l;                                     // :73
+        const double g3 = P::g_row_dfdx(Y4, uB, k4, s4, rp);       // :74-75
+        const double k3 = __builtin_fma(c.h, g3, h3l);             // :77
+        const double g2 = P::g_row_dfdx(Y3, uM, k3, s3, rp);       // :78-79
+        const double k2 = __builtin_fma(c.hh, g2, h3l);            // :81
+        const double g1 = P::g_row_dfdx(Y2, uM, k2, s3, rp);       // :82-83
+        const double k1 = __builtin_fma(c.hh, g1, h6l);            // :85
+        const double g0 = P::g_row_dfdx(xi, uA, k1, s1, rp);       // :87-88
+        lam = (((lam + g1) + g2) + g3) + g0;                       // :86-88
+        if (OUT_DJDU) {                                            // compute_dJdu :97-121
+          const double p4 = P::g_row_dfdu(Y4, uB, k4, s4, rp);
+          p23 = P::g_row_dfdu(Y3, uM, k3, s3, rp) + P::g_row_dfdu(Y2, uM, k2, s3, rp);
+          pn = pend + p4;
+          pend = P::g_row_dfdu(xi, uA, k1, s1, rp);
+          if (q == 0) {
+            // column 2 lo = B'k1 of step lo + B'k4 of step lo-1 (k4 = h/6 lam_lo); column 0 has the k1 half only
+            // :101-102.  Where (dF/du)'v reads y, stage state 4 of the step below is recomputed from three extra loads.
+            const Rc cb = rec_of(rw, -1);
+            const Stage sb4 = P::template stage<LT>(cb.s4, cb.h6, cb.tB, lamc);
+            double Y4b = 0.0;
+            if (P::DFDU_READS_Y) {
+              double fb = P::g_row_f(d.xb, d.ub0, cb.tA, rp);
+              const double Y2b = __builtin_fma(cb.hh, fb, d.xb);
+              fb = P::g_row_f(Y2b, d.ub1, cb.tM, rp);
+              const double Y3b = __builtin_fma(cb.hh, fb, d.xb);
+              fb = P::g_row_f(Y3b, d.ub1, cb.tM, rp);
+              Y4b = __builtin_fma(cb.h, fb, d.xb);
+            }
+            pb = pend + P::g_row_dfdu(Y4b, uA, cb.h6 * lam, sb4, rp);
+          }
+        }
+      }
       if (OUT_LAM) bl.st(lam, vl, (unsigned)q * col8);
-      if (OUT_DJDU) {                                            // compute_dJdu :97-121
-        const double p4 = P::g_row_dfdu(Y4, uB, k4, s4, rp);
-        const double p23 = P::g_row_dfdu(Y3, uM, k3, s3, rp) + P::g_row_dfdu(Y2, uM, k2, s3, rp);
-        // column 2i+1 (sum of p23 over the rows) and column 2i+2 (sum of pend + p4; it belongs to the chunk of step
-        // i+1, except column 2N): lanes of row 0 end up with the first, lanes of row 1 with the second
+      if (OUT_DJDU) {
+        // column 2i+1 (sum of p23 over the rows) and column 2i+2 (sum of pn; it belongs to the chunk of step i+1,
+        // except column 2N): lanes of row 0 end up with the first, lanes of row 1 with the second
         double cmid, cnode;
         if (G == 1) {
           cmid = p23;
-          cnode = pend + p4;
+          cnode = pn;
         } else {
-          cmid = cnode = pair_sum_sc<G>(p23, pend + p4);
+          cmid = cnode = pair_sum_sc<G>(p23, pn);
         }
-        pend = P::g_row_dfdu(xi, uA, k1, s1, rp);
         const unsigned so = (unsigned)(2 * q) * B8;
-        double cbot = 0.0;
-        if (q == 0) {
-          // column 2 lo = B'k1 of step lo + B'k4 of step lo-1 (k4 = h/6 lam_lo); column 0 has the k1 half only
-          // :101-102.  Where (dF/du)'v reads y, stage state 4 of the step below is recomputed from three extra loads.
-          const Rc cb = rec_of(rw, -1);
-          const Stage sb4 = P::template stage<LT>(cb.s4, cb.h6, cb.tB, lamc);
-          double Y4b = 0.0;
-          if (P::DFDU_READS_Y) {
-            double fb = P::g_row_f(d.xb, d.ub0, cb.tA, rp);
-            const double Y2b = __builtin_fma(cb.hh, fb, d.xb);
-            fb = P::g_row_f(Y2b, d.ub1, cb.tM, rp);
-            const double Y3b = __builtin_fma(cb.hh, fb, d.xb);
-            fb = P::g_row_f(Y3b, d.ub1, cb.tM, rp);
-            Y4b = __builtin_fma(cb.h, fb, d.xb);
-          }
-          cbot = group_sum_sc<G>(pend + P::g_row_dfdu(Y4b, uA, cb.h6 * lam, sb4, rp));
-        }
+        const double cbot = (q == 0) ? group_sum_sc<G>(pb) : 0.0;
         if (G == 1) {
           bd.st(cmid, vd_mid, so);
           if (q == L - 1)
@@ -382,7 +451,8 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
             bd.st(cnode, vd_node, so);
           if (q == 0) bd.st(cbot, vd_bot, so);
         } else {
-          const double val = is0 ? cmid : (is1 ? cnode : cbot);
+          // (cmid = cnode here; above q = 0 the lanes of rows 2 and 3 store nothing)
+          const double val = (q == 0 && !is0 && !is1) ? cbot : cmid;
           if (q == L - 1)
             bd.st(val, (topc | is0) ? vd_r : kOffDrop, so);
           else if (q == 0 && G == 4)
