@@ -263,7 +263,11 @@ int ocs_control_set_fusion(ocs_control c, int mode);
  * Gen-1 drivers run on a Gen-2 OCProblem through the adapter stateRHS = F(1:nS), objective = F(end),
  * adjointRHS = -dFdx_times_vec(t,[x;0],u,[lam;1])(1:nS), ControlChar = clamp(argzero dFdu_times_vec(...))
  * (make_from_symbolic.m:11-23,111).  odevr7 is replaced by RK4 on the grid of `g` (an RK4Integrator),
- * x(t)/lam(t) are pchip interpolants of the node values as in compute_x_lam.m:9,14. */
+ * x(t)/lam(t) are pchip interpolants of the node values as in compute_x_lam.m:9,14.
+ * OCS_PROBLEM_LQ: from 8 states on the state pass and the costate pass run on the problem's matrix-core kernels
+ * (ocs_fb_sweep_matrix_core); the control update, the error points and the bookkeeping run on the same problem written
+ * as generated device source (compiled once per handle), as do all passes with 7 states or fewer.  Per-trajectory
+ * parameters are refused on this problem (OCS_ERR_UNSUPPORTED). */
 /* Fill the struct with ocs_fbs_default_options before setting fields: it has grown at its end between builds (uRelax
  * is the latest member) and may again; a caller compiled against an older header passes a shorter struct. */
 typedef struct ocs_fbs_options {
@@ -316,6 +320,11 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double *x
  * the costate alone); 5 the sequence of 1 with the error points off the grid nodes (or a given u0), its kernels gated and
  * enqueued ahead like 2. */
 int ocs_fb_sweep_path(ocs_integrator g);
+/* Diagnostic: 1 if the last ocs_fb_sweep(_dev) / ocs_compute_x_lam(_dev) on this integrator ran its state pass and its
+ * costate pass on the matrix-core kernels of OCS_PROBLEM_LQ (csrc/ocs_lq_sweep_kernels.hip: an RK4Integrator grid, 8 to 32
+ * states, no per-trajectory parameters); 0 otherwise, or if none has run.  It does not change ocs_fb_sweep_path: the
+ * sweep loops are the same, only the two passes inside them differ. */
+int ocs_fb_sweep_matrix_core(ocs_integrator g);
 
 /* ---- the batch axis over the GPUs of one node (the reference has no batch axis and no parallelism:
  * every entry point integrates one trajectory, tests/solve_test_problem.m:37) ----

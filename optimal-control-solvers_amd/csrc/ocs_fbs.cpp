@@ -19,6 +19,17 @@ struct ocs_fbs_state {
   int nerr = 0, nint = 0;
   bool err_on_nodes = false;  // the error points are the grid nodes (the default on a linspace tspan)
   int last_path = 0;          // ocs_fb_sweep_path
+  int last_matrix_core = 0;   // ocs_fb_sweep_matrix_core
+  // The LQ problem's own time-coefficient table and step records (StepRec<1>: e^{-rt} at A / M / B) for the matrix-core
+  // state and costate passes (ocs_lq_sweep_kernels.hip).  The integrator's tables (bind_problem) stay those of the plugin
+  // twin, which the other kernels of the sweep run; these are keyed on (LQ problem, its version, grid) and ordered for
+  // stream switches like the integrator's tc_event.
+  DevBuf lq_TC, lq_REC;
+  const ocs_problem_s* lq_prob = nullptr;
+  unsigned long long lq_version = 0;
+  int lq_N = -1;
+  hipEvent_t lq_event = nullptr;
+  hipStream_t lq_stream = nullptr;
   DevBuf KE, SE, TE, TUE, KI, SI, TI, TUI;
   DevBuf QSE;   // error points by interval: offsets [n] (they are sorted: linspace)
   unsigned long long tu_version = 0;
@@ -40,6 +51,9 @@ void ocs_fbs_state_free(ocs_fbs_state* s) {
                     &s->usel, &s->status, &s->maxchange, &s->nactive, &s->x0, &s->stage, &s->metric, &s->anyvalid, &s->dump};
   for (DevBuf* b : bufs) b->release();
   s->nact_slots.release();
+  s->lq_TC.release();
+  s->lq_REC.release();
+  if (s->lq_event) (void)hipEventDestroy(s->lq_event);
   for (hipEvent_t e : s->wevents) (void)hipEventDestroy(e);
   if (s->h_nact) (void)hipHostFree(s->h_nact);
   delete s;
@@ -361,6 +375,50 @@ static int sweep_problem(ocs_problem_s* p, ocs_problem_s** out) {
   return OCS_OK;
 }
 
+// The state pass and the costate pass of the sweep on the matrix-core kernels of the LQ problem itself
+// (ocs_lq_sweep_kernels.hip) instead of the twin's lane kernels, from the first state count at which they are faster at
+// batch 1024 (table: NOTES.md "fb_sweep on the LQ problem by state count", profiles/lq_sweep_ab.log); below it the twin
+// runs every pass.  OCS_LQ_SWEEP=0 restores the twin-only path (A/B runs).
+constexpr int kLqSweepMinStates = 8;
+static bool lq_sweep_ok(const ocs_problem_s* p, const ocs_integrator_s* g) {
+  static const bool off = getenv("OCS_LQ_SWEEP") && getenv("OCS_LQ_SWEEP")[0] == '0';
+  return !off && p->functor == Functor::LQ && lq_supported(p->nS, p->nC) && !p->pmask && g->kind == 0 &&
+         p->nS >= kLqSweepMinStates;
+}
+// make sure the LQ step records of (g, p) are current (enqueued on `s`); *out: the grid with them in place of the bound problem's
+// (keyed like bind_problem's tables: a freed problem's address may be reused by a new handle, its version is not --
+//  next_version() is unique over all handles of the process, ocs_handles.hpp)
+static int lq_sweep_bind(ocs_integrator_s* g, ocs_problem_s* p, hipStream_t s, GridDesc* out) {
+  OCS_TRY(upload_problem(p));
+  OCS_TRY(upload_grid(g));
+  ocs_fbs_state* f = g->fbs;
+  const int rs = rec_stride_host(1), pad = rec_pad_host();
+  const bool stale = f->lq_prob != p || f->lq_version != p->version || f->lq_N != g->N;
+  if (stale) {
+    OCS_TRY(f->lq_TC.ensure(sizeof(double) * (size_t)(2 * g->N + 1)));
+    OCS_TRY(f->lq_REC.ensure(sizeof(double) * (size_t)(g->N + 2 * pad) * rs));
+  }
+  GridDesc d = describe(g);
+  d.TC = f->lq_TC.d();
+  d.TU = nullptr;   // (the ControlChar side stays the twin's)
+  d.REC = f->lq_REC.d() + (size_t)pad * rs;
+  d.RECS = nullptr;
+  d.lqws = nullptr;
+  if (stale) {
+    LAUNCH_TRY(launch_tcoef_lq(describe(p), d, s));
+    f->lq_prob = p;
+    f->lq_version = p->version;
+    f->lq_N = g->N;
+    if (!f->lq_event) HIP_TRY(hipEventCreateWithFlags(&f->lq_event, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(f->lq_event, s));
+    f->lq_stream = s;
+  } else if (f->lq_event && s != f->lq_stream) {
+    HIP_TRY(hipStreamWaitEvent(s, f->lq_event, 0));
+  }
+  *out = d;
+  return OCS_OK;
+}
+
 // value = ControlChar(t, x, lam): the Gen-1 problem method of make_from_symbolic.m:33-38 with the clamp of :111, which fb_sweep
 // evaluates on pchip x, lam (fb_sweep.m:96, 123); host pointers, MATLAB shapes: t k, x and lam nS x k, out nC x k.
 int ocs_problem_ControlChar(ocs_problem p, int k, const double* t, const double* x, const double* lam, double* out) {
@@ -401,11 +459,14 @@ int ocs_compute_x_lam_dev(ocs_integrator g, ocs_problem p, int batch, const doub
   OCS_TRACE("ocs_compute_x_lam_dev");
   if (!g || !p || !x0 || !ugrid || !xaug || !lam || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
   if (g->kind != 0) return fail(OCS_ERR_UNSUPPORTED, "compute_x_lam needs an RK4Integrator grid");
+  ocs_problem_s* const lqp = p;   // the handle the caller gave: for OCS_PROBLEM_LQ the matrix-core passes run it
+  if (g->fbs) g->fbs->last_matrix_core = 0;   // (a call that fails below reports 0, not the flag of the call before it)
   OCS_TRY(sweep_problem(p, &p));
   hipStream_t s = (hipStream_t)stream;
   OCS_TRY(bind_problem(g, p, batch, s));
   OCS_TRY(ensure_tables(g));
   ocs_fbs_state* f = g->fbs;
+  f->last_matrix_core = 0;
   const int N = g->N, nS = p->nS, nAug = nS + 1;
   const size_t B = (size_t)batch;
   OCS_TRY(f->xmid.ensure(sizeof(double) * (size_t)N * nS * B));
@@ -413,6 +474,17 @@ int ocs_compute_x_lam_dev(ocs_integrator g, ocs_problem p, int batch, const doub
   if (!Jd) {
     OCS_TRY(f->J.ensure(sizeof(double) * B));
     Jd = f->J.d();
+  }
+  if (lq_sweep_ok(lqp, g)) {
+    GridDesc lqg;
+    OCS_TRY(lq_sweep_bind(g, lqp, s, &lqg));
+    const ProblemDesc lqd = describe(lqp);
+    const FbsTables tb = tabs(g);
+    f->last_matrix_core = 1;
+    LAUNCH_TRY(launch_sweep_forward_lq(lqd, lqg, batch, x0, ugrid, xaug, Jd, nullptr, nullptr, s));
+    LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s));
+    LAUNCH_TRY(launch_sweep_costate_lq(lqd, lqg, batch, xaug, nAug, f->xmid.d(), nullptr, lam, nullptr, s));
+    return OCS_OK;
   }
   LAUNCH_TRY(launch_forward(describe(p), describe(g), batch, x0, ugrid, xaug, Jd, FwdOpts(), s));
   const FbsTables tb = tabs(g);
@@ -438,6 +510,8 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   if (!g || !p || !x0 || !opt || !xaug || !lam || !uInterp || !J || !sweeps || batch < 1)
     return fail(OCS_ERR_INVALID, "bad argument");
   if (g->kind != 0) return fail(OCS_ERR_UNSUPPORTED, "fb_sweep needs an RK4Integrator grid");
+  ocs_problem_s* const lqp = p;   // the handle the caller gave: for OCS_PROBLEM_LQ the matrix-core passes run it
+  if (g->fbs) g->fbs->last_matrix_core = 0;   // (a call that fails below reports 0, not the flag of the call before it)
   OCS_TRY(sweep_problem(p, &p));
   if (p->user && !p->user->has_cc)
     return fail(OCS_ERR_UNSUPPORTED, "fb_sweep needs ocs_ControlChar in the user problem source (has_control_char)");
@@ -501,12 +575,33 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   const ProblemDesc pd = describe(p);
   const GridDesc gd = describe(g);
   const FbsTables tb = tabs(g);
+  // The LQ problem: state and costate pass of every loop below on the matrix-core kernels, with the problem's own
+  // descriptor and step records; everything else (midpoints, control update, error points, bookkeeping) on the twin `pd`.
+  // The `!lqmc` in `fold` and `ownx` below changes no path number: the twin is full-vector source with nS >= 8, for which
+  // fold_supported (nC == 1 and nS in {1, 2, 4}) and costate_forms_midpoints (user_vector: nS <= 4; row functions: nS in
+  // {1, 2, 4}) are false already -- it states that the matrix-core costate pass needs the xmid array of launch_pchip_mid.
+  const bool lqmc = lq_sweep_ok(lqp, g);
+  f->last_matrix_core = lqmc ? 1 : 0;
+  ProblemDesc lqd = pd;
+  GridDesc lqg = gd;
+  if (lqmc) {
+    OCS_TRY(lq_sweep_bind(g, lqp, s, &lqg));
+    lqd = describe(lqp);
+  }
+  auto state_pass = [&](const FwdOpts& fo) -> int {
+    if (lqmc) return launch_sweep_forward_lq(lqd, lqg, batch, x0, f->ugrid.d(), xaug, J, fo.frozen, fo.gate, s);
+    return launch_forward(pd, gd, batch, x0, f->ugrid.d(), xaug, J, fo, s);
+  };
+  auto costate_pass = [&](const double* xmid, const double* PR, const int* gate) -> int {
+    if (lqmc) return xmid ? launch_sweep_costate_lq(lqd, lqg, batch, xaug, nAug, xmid, status, lam, gate, s) : -1;
+    return launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, PR, gate);
+  };
   // every sweep with the control update folded into the state pass (see below): the grid samples of u are never formed
   // (not with a damped update: that needs the samples of the control it damps)
   // (registry problems: where the wave-specialised costate kernels and the gated state pass apply; hipRTC problems: row
   //  functions whose ocs_ControlChar reads the costate alone, fold_supported)
   const bool userfold = p->user != nullptr && fold_supported(pd, gd, batch);
-  const bool fold = fusedup && om == 1.0 && opt->fused_update_off == 0 &&
+  const bool fold = !lqmc && fusedup && om == 1.0 && opt->fused_update_off == 0 &&
                     (userfold || (costate_forms_midpoints(pd, N, batch) && forward_gate_supported(pd, gd, batch) &&
                                   fold_supported(pd, gd, batch)));
   if (u0grid) {  // u = u0  :76
@@ -535,7 +630,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   const bool ahead1 = !fusedup && fuo == 0 && forward_gate_any(pd);
   if ((fusedup && (fold || forward_gate_any(pd))) || ahead1) {
     const int nsw = opt->nSWEEPS;
-    const bool ownx = fuo == 0 && costate_forms_midpoints(pd, N, batch);   // midpoints inside the costate / control kernels
+    const bool ownx = !lqmc && fuo == 0 && costate_forms_midpoints(pd, N, batch);   // midpoints inside the costate / control kernels
     f->last_path = fold ? 4 : (fusedup ? 2 : 5);
     if (f->h_nact_cap < nsw) {
       if (f->h_nact) (void)hipHostFree(f->h_nact);
@@ -584,11 +679,10 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
       fo.dump = f->dump.d();
       fo.no_cost_row = opt->cost_row == 0;
       fo.gate = gate;
-      LAUNCH_TRY(launch_forward(pd, gd, batch, x0, f->ugrid.d(), xaug, J, fo, s));
+      LAUNCH_TRY(state_pass(fo));
       const double* xmid = ownx ? nullptr : f->xmid.d();
       if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s, gate));
-      LAUNCH_TRY(launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, tb.PR,
-                                gate));
+      LAUNCH_TRY(costate_pass(xmid, tb.PR, gate));
       if (!fusedup) {   // error points off the nodes: uNew there with check_convergence (:96, :99-115), then u = uNew on the grid
         if (cps)
           LAUNCH_TRY(launch_control_pts_sorted(pd, tb, nE, (const int*)f->QSE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
@@ -631,9 +725,9 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
     fo.frozen = status;
     fo.dump = f->dump.d();
     fo.no_cost_row = opt->cost_row == 0;  // soln holds x, lam, u and the scalar J (fb_sweep.m:117-125)
-    LAUNCH_TRY(launch_forward(pd, gd, batch, x0, f->ugrid.d(), xaug, J, fo, s));
+    LAUNCH_TRY(state_pass(fo));
     // pchip midpoints of x: inside the costate and control kernels where the wave-specialised costate kernel applies
-    const bool ownx = fusedup && fuo == 0 && costate_forms_midpoints(pd, N, batch);
+    const bool ownx = !lqmc && fusedup && fuo == 0 && costate_forms_midpoints(pd, N, batch);
     const double* xmid = ownx ? nullptr : f->xmid.d();
     if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s));
     HIP_TRY(hipMemsetAsync(f->nactive.p, 0, sizeof(int), s));
@@ -641,7 +735,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
       // costate (:95); uNew = ControlChar(t, x(t), lam(t)) on the grid, in place (:96, :85), with the weighted change at
       // the nodes (:107) folded in.  A just-converged instance takes uNew as well, but it is frozen from now on: its
       // x, lam, J are the ones computed above from the old control, which is what final_sweep(u) returns (:82).
-      LAUNCH_TRY(launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, tb.PR));
+      LAUNCH_TRY(costate_pass(xmid, tb.PR, nullptr));
       LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, f->metric.d(),
                                      opt->uRelTol, opt->uAbsTol, s, nullptr, om));
       LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
@@ -650,7 +744,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
       HIP_TRY(hipStreamSynchronize(s));
       continue;
     }
-    LAUNCH_TRY(launch_costate(pd, gd, batch, xaug, nAug, f->xmid.d(), f->ugrid.d(), status, f->dump.d(), lam, s));
+    LAUNCH_TRY(costate_pass(f->xmid.d(), nullptr, nullptr));
     // ... uNew = ControlChar(t, x(t), lam(t)) (:96) on the error points, with check_convergence(uNew, u)
     // (:81, :99-115) folded in
     if (cps)
@@ -679,6 +773,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
 }
 
 int ocs_fb_sweep_path(ocs_integrator g) { return (g && g->fbs) ? g->fbs->last_path : 0; }
+int ocs_fb_sweep_matrix_core(ocs_integrator g) { return (g && g->fbs) ? g->fbs->last_matrix_core : 0; }
 
 // host: x0 nS x batch; u0grid nC x (2N+1) x batch, u0err nC x nERR x batch (or both NULL);
 // x nS x (N+1) x batch, lam nS x (N+1) x batch, uInterp nC x nINTERP x batch, J batch, sweeps batch,

@@ -135,6 +135,14 @@ int launch_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const 
                       double* x, double* J, const FwdOpts& o, hipStream_t s);
 int launch_backward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
                        const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s);
+// fb_sweep's state and costate passes of the same problem on the matrix cores (ocs_lq_sweep_kernels.hip), one wave per
+// 16 trajectories.  g.REC: the LQ problem's own step records (launch_tcoef_lq), not those of the integrator's bound
+// problem.  frozen / gate as FwdOpts; stores of frozen instances are dropped, no scratch array.  x [N+1][ldx][B] with
+// ldx = nS + 1, xmid [N][nS][B] (launch_pchip_mid), lam [N+1][nS][B].  The costate pass reads no control samples.
+int launch_sweep_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
+                            double* x, double* J, const int* frozen, const int* gate, hipStream_t s);
+int launch_sweep_costate_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx,
+                            const double* xmid, const int* frozen, double* lam, const int* gate, hipStream_t s);
 // 'nearest' / 'next' of griddedInterpolant: index of the sample a query point takes, -1 = NaN (ocs_control.cpp)
 int interp_sample_index(int method, int n, const double* x, double q);
 int launch_eval_lq(const ProblemDesc& p, int which, int k, const double* t, const double* y, const double* u,

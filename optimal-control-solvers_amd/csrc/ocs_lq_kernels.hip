@@ -20,6 +20,7 @@
 // (bit-identical to the forward pass) and runs the four A'k products on the transposed fragments.
 #include "ocs_device_common.hpp"
 #include "ocs_internal.hpp"
+#include "ocs_lq_core.hpp"       // mma, LQMat, load_frags, matvec, LQCore, LQArgs, LQTime
 #include "ocs_rk4_kernels.hpp"
 #include "ocs_scan_kernel.hpp"   // Buf: raw buffer accesses with scalar offsets
 #include <cstdlib>
@@ -33,154 +34,12 @@ namespace ocs {
 
 static inline int hip_rc_lq(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-// time coefficients of the LQ problem for the shared table builders (k_tcoef / k_build_rec)
-struct LQTime {
-  static constexpr int NTC = 1, NTU = 1, NSC = 0;
-  __device__ static inline void tcoef(double t, const double* ps, double* tc, double* tu) {
-    tc[0] = exp(-ps[0] * t);
-    tu[0] = exp(ps[0] * t);
-  }
-  __device__ static inline void step_consts(double, double, const double*, const double*, const double*, double*) {}
-};
-
 int launch_tcoef_lq(const ProblemDesc& p, const GridDesc& g, hipStream_t s) {
   const int nT = 2 * g.N + 1;
   k_tcoef<LQTime><<<dim3((nT + 255) / 256), dim3(256), 0, s>>>(nT, g.T, p.ps, g.TC, g.TU);
   k_build_rec<LQTime><<<dim3((g.N + 2 * kRecPad + 255) / 256), dim3(256), 0, s>>>(g.N, g.HT, g.TC, g.REC);
   return hip_rc_lq(hipGetLastError());
 }
-
-struct LQArgs {
-  int N, batch, nS, nC;
-  const double* REC;
-  const double* ps;     // [r | A nS x nS col-major | Bu nS x nC | q nS | rdiag nC]
-  const double* x0;     // forward: [nS][B]
-  const double* xck;    // backward: checkpoints [N+1][nAug][B]
-  const double* u;      // [2N+1][nC][B]; UCONST: [nC]
-  double* x;            // forward out [N+1][nAug][B] or null
-  double* J;            // forward out [B]
-  const double* Jadd;   // optional [B]
-  const double* lamT;   // backward: [nAug][B] or null (default e_last, RK4Integrator.m:63-66)
-  double* lam;          // [N+1][nAug][B] or null
-  double* dJdu;         // [2N+1][nC][B] or null
-  double* lam0;         // [nAug][B] or null
-  long long* dbg;       // diagnostic builds only: [blocks][8] cycle sums
-  // time-parallel passes (k_lq_forward / k_lq_backward with CH != 0): blockIdx.y = chunk c, steps [c L, min(N, (c+1) L))
-  int L;                // steps per chunk
-  const double* cs;     // chunk start values [C][nS][B]: the state at the chunk's first node / the costate at its last node
-  double* ce;           // CH = 1: chunk end values [C][nS][B] (state at the last node from cs / costate at the first node from 0)
-  double* cj;           // CH = 2: forward: chunk objective sums [C][B]; adjoint: k1 half of the chunk's first node column [C][nC][B]
-};
-
-// D = A(16x4) * B(4x16) + C on one wave; a: lane (g,i) holds A[i][g]; b: lane (g,n) holds B[g][n];
-// c/d: lane (g,n) holds rows g + 4j of column n.
-__device__ static inline d4 mma(double a, double b, d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-template <int RT>
-struct LQMat {
-  static constexpr int KS = 4 * RT;
-  double f[RT][KS];
-};
-
-// fragments of M (rows x cols, column-major with leading dimension ld, zero outside) as the A operand:
-// tile rt, k-step kk: lane (g,i) <- M[16 rt + i][4 kk + g];  TRANS reads M' instead.
-template <int RT, bool TRANS>
-__device__ static inline void load_frags(LQMat<RT>& o, const double* M, int ld, int rows, int cols, int g, int i) {
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int kk = 0; kk < 4 * RT; ++kk) {
-      const int r = 16 * rt + i, c = 4 * kk + g;
-      const int rr = TRANS ? c : r, cc = TRANS ? r : c;
-      o.f[rt][kk] = (rr < rows && cc < cols) ? M[rr + (size_t)ld * cc] : 0.0;
-    }
-}
-
-// acc (tile rt, reg j) <-> row 4 (4 rt + j) + g, i.e. per-lane value index m = 4 rt + j
-template <int RT>
-__device__ static inline void matvec(const LQMat<RT>& A, const double (&v)[4 * RT], d4 (&acc)[RT]) {
-  if constexpr (RT == 1) {  // a single tile: two independent accumulation chains instead of one dependent one
-    d4 alt = {0.0, 0.0, 0.0, 0.0};
-    acc[0] = mma(A.f[0][0], v[0], acc[0]);
-    alt = mma(A.f[0][1], v[1], alt);
-    acc[0] = mma(A.f[0][2], v[2], acc[0]);
-    alt = mma(A.f[0][3], v[3], alt);
-    acc[0] += alt;
-  } else {
-#pragma unroll
-    for (int kk = 0; kk < 4 * RT; ++kk)
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[rt] = mma(A.f[rt][kk], v[kk], acc[rt]);
-  }
-}
-
-template <int RT>
-__device__ static inline void unpack(const d4 (&acc)[RT], double (&f)[4 * RT]) {
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    f[4 * rt + 0] = acc[rt].x;
-    f[4 * rt + 1] = acc[rt].y;
-    f[4 * rt + 2] = acc[rt].z;
-    f[4 * rt + 3] = acc[rt].w;
-  }
-}
-
-// sum over the four lanes (g = 0..3) that share a trajectory
-__device__ static inline double sum_over_g(double v) {
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
-template <int RT>
-struct LQCore {
-  static constexpr int KS = 4 * RT;
-  LQMat<RT> A;
-  double Bu[RT];   // A-operand fragments of Bu (nS x nC, K = 4 >= nC): lane (g,i) <- Bu[16 rt + i][g]
-  double q[KS];    // q[4m + g]
-  double R;        // rdiag[g] (0 for g >= nC)
-
-  __device__ inline void load(const double* ps, int nS, int nC, int g, int i) {
-    load_frags<RT, false>(A, ps + 1, nS, nS, nS, g, i);
-    const double* bu = ps + 1 + (size_t)nS * nS;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      const int r = 16 * rt + i;
-      Bu[rt] = (r < nS && g < nC) ? bu[r + (size_t)nS * g] : 0.0;
-    }
-    const double* qq = bu + (size_t)nS * nC;
-#pragma unroll
-    for (int m = 0; m < KS; ++m) q[m] = (4 * m + g < nS) ? qq[4 * m + g] : 0.0;
-    R = (g < nC) ? qq[nS + g] : 0.0;
-  }
-  // Bu * u for 16 trajectories (lane (g,n) holds u_g of trajectory n)
-  __device__ inline void bu_times(double u, d4 (&o)[RT]) const {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      const d4 z = {0.0, 0.0, 0.0, 0.0};
-      o[rt] = mma(Bu[rt], u, z);
-    }
-  }
-  // state rows of F: A Y + Bu u (bu = Bu u precomputed)
-  __device__ inline void Fx(const double (&Y)[KS], const d4 (&bu)[RT], double (&f)[KS]) const {
-    d4 acc[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[rt] = bu[rt];
-    matvec<RT>(A, Y, acc);
-    unpack<RT>(acc, f);
-  }
-  // this lane's share of the objective integrand e^{-rt}(sum q x^2 + sum R u^2)
-  __device__ inline double cost_part(const double (&Y)[KS], double u, double e) const {
-    double s = R * (u * u);
-#pragma unroll
-    for (int m = 0; m < KS; ++m) s = __builtin_fma(q[m], Y[m] * Y[m], s);
-    return e * s;
-  }
-};
 
 // ---------------------------------------------------------------------------------------
 // forward pass   RK4Integrator.m:28-56

@@ -126,6 +126,12 @@ def fb_sweep_path(integrator):
     return int(lib.ocs_fb_sweep_path(integrator._h))
 
 
+def fb_sweep_matrix_core(integrator):
+    """Diagnostic (ocs.h ocs_fb_sweep_matrix_core): 1 if the last fb_sweep / compute_x_lam(_J) on this integrator ran its state
+    and costate passes on the matrix-core kernels of LQProblem (8 to 32 states), 0 otherwise or if none has run."""
+    return int(lib.ocs_fb_sweep_matrix_core(integrator._h))
+
+
 def fb_sweep(prob, x0, tspan, options=None):
     """soln = fb_sweep(prob, x0, tspan, options)   fb_sweep.m:1.  Returns a dict with the callables
     x, lam, u (pchip interpolants, vectorInterpolant.m) and J, or an empty dict when the sweep did not
