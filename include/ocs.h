@@ -45,7 +45,8 @@ extern "C" {
 /* ---- problem registry (device functors; see csrc/ocs_problems.hpp) ---- */
 #define OCS_PROBLEM_TEST 1     /* tests/TestOCProblem.m:22-38        params [c m r], nS=1, nC=1 */
 #define OCS_PROBLEM_LOGISTIC 2 /* LogisticK       params [c r m_1..m_nS], nC=1 */
-#define OCS_PROBLEM_LQ 3       /* linear-quadratic, shared Jacobian  params [r | A | Bu | q | rdiag], nS<=32, nC<=4 */
+#define OCS_PROBLEM_LQ 3       /* linear-quadratic, shared Jacobian  params [r | A | Bu | q | rdiag], nS<=32, nC<=4;
+                                * q and rdiag may differ per trajectory (ocs_problem_set_batch_params), r, A and Bu are shared */
 #define OCS_PROBLEM_USER 100   /* plugin methods given as device source (ocs_problem_create_from_source) */
 
 /* ---- control parametrisations ---- */
@@ -101,7 +102,18 @@ int ocs_problem_check_source(const char *source, int nS, int nC, int nparams, in
 int ocs_problem_destroy(ocs_problem p);
 int ocs_problem_dims(ocs_problem p, int *nS, int *nC);
 /* Per-trajectory overrides of scalar parameters (batch extension; the reference has one
- * parameter set per call).  values: nidx x batch column-major; param_index: 0-based into params. */
+ * parameter set per call).  values: nidx x batch column-major; param_index: 0-based into params.  nidx == 0 clears them.
+ * Calls on the problem must then use that batch (OCS_ERR_SHAPE otherwise).  At most 32 parameters, none of them feeding
+ * the time-coefficient table (OCS_ERR_UNSUPPORTED).
+ * OCS_PROBLEM_LQ: an index set that lies in the weight range of [r | A | Bu | q | rdiag] -- indices
+ * 1 + nS*nS + nS*nC .. nparams-1, for every supported nS and nC, whatever the size of the block -- gives every trajectory
+ * its own cost weights q and rdiag (entries not named keep the shared values).  ocs_compute_states / ocs_compute_adjoints
+ * and what is built on them (RK4InfiniteIntegrator, ocs_nlp_objective, ocs_single_shooting_batch, ocs_multi_*: each
+ * device's block on that device's handle) then run per trajectory, on every mapping.  ocs_fb_sweep*, ocs_compute_x_lam*
+ * and ocs_problem_ControlChar refuse such a problem (their control update reads the shared rdiag), as do ocs_problem_F /
+ * _dFdx_times_vec / _dFdu_times_vec, whose k free columns have no trajectory index (OCS_ERR_UNSUPPORTED).  A set that
+ * names r or an entry of A or Bu is handled as for any problem: refused if the block has more than 32 entries, otherwise
+ * accepted -- but no kernel of this problem reads such overrides, every pass then fails with OCS_ERR_UNSUPPORTED. */
 int ocs_problem_set_batch_params(ocs_problem p, int batch, const int *param_index, int nidx,
                                  const double *values);
 /* value = F / dFdx_times_vec / dFdu_times_vec (OCProblem.m:12,16,19; TestOCProblem.m:22-38)
@@ -267,7 +279,7 @@ int ocs_control_set_fusion(ocs_control c, int mode);
  * OCS_PROBLEM_LQ: from 8 states on the state pass and the costate pass run on the problem's matrix-core kernels
  * (ocs_fb_sweep_matrix_core); the control update, the error points and the bookkeeping run on the same problem written
  * as generated device source (compiled once per handle), as do all passes with 7 states or fewer.  Per-trajectory
- * parameters are refused on this problem (OCS_ERR_UNSUPPORTED). */
+ * parameters, cost weights included, are refused on this problem (OCS_ERR_UNSUPPORTED). */
 /* Fill the struct with ocs_fbs_default_options before setting fields: it has grown at its end between builds (uRelax
  * is the latest member) and may again; a caller compiled against an older header passes a shorter struct. */
 typedef struct ocs_fbs_options {

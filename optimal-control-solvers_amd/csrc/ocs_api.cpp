@@ -92,6 +92,7 @@ int ocs_problem_destroy(ocs_problem p) {
   if (p->user) jit_free(p->user);
   p->d_ps.release();
   p->d_pb.release();
+  p->d_w.release();
   p->d_lb.release();
   p->d_ub.release();
   delete p;
@@ -110,6 +111,7 @@ int ocs_problem_set_batch_params(ocs_problem p, int batch, const int* param_inde
   if (!p) return fail(OCS_ERR_INVALID, "null problem");
   if (nidx == 0) {  // clear
     p->pmask = 0;
+    p->has_w = false;
     p->pb_batch = 0;
     p->version = next_version();
     return OCS_OK;
@@ -117,6 +119,28 @@ int ocs_problem_set_batch_params(ocs_problem p, int batch, const int* param_inde
   if (!param_index || !values || batch < 1 || nidx < 0) return fail(OCS_ERR_INVALID, "bad argument");
   OCS_TRY(upload_problem(p));
   const int npar = (int)p->par.size();
+  if (p->functor == Functor::LQ) {
+    // The cost weights q and rdiag (the tail of [r | A | Bu | q | rdiag]) are per-lane registers of the matrix-core kernels and
+    // may differ per trajectory; an index set inside that range goes to a dense array of its own, W [nS + nC][batch], which
+    // holds every trajectory's full q and rdiag (rows not named: the shared values).  Any other set takes the mask path below.
+    const int w0 = 1 + p->nS * p->nS + p->nS * p->nC, nW = p->nS + p->nC;
+    bool weights_only = true;
+    for (int q = 0; q < nidx; ++q) weights_only = weights_only && param_index[q] >= w0 && param_index[q] < npar;
+    if (weights_only) {
+      std::vector<double> W((size_t)nW * batch);
+      for (int r = 0; r < nW; ++r)
+        for (int b = 0; b < batch; ++b) W[(size_t)r * batch + b] = p->par[w0 + r];
+      for (int q = 0; q < nidx; ++q)
+        for (int b = 0; b < batch; ++b) W[(size_t)(param_index[q] - w0) * batch + b] = values[(size_t)b * nidx + q];
+      OCS_TRY(p->d_w.ensure(sizeof(double) * W.size()));
+      HIP_TRY(hipMemcpy(p->d_w.p, W.data(), sizeof(double) * W.size(), hipMemcpyHostToDevice));
+      p->pmask = 0;
+      p->has_w = true;
+      p->pb_batch = batch;
+      p->version = next_version();
+      return OCS_OK;
+    }
+  }
   if (npar > 32) return fail(OCS_ERR_UNSUPPORTED, "per-trajectory parameters need <= 32 parameters");
   if (p->user && (npar > 16 || user_rowsep(p->user)))
     return fail(OCS_ERR_UNSUPPORTED, "user problems with more than 16 parameters or given as row functions read the "
@@ -140,6 +164,7 @@ int ocs_problem_set_batch_params(ocs_problem p, int batch, const int* param_inde
   OCS_TRY(p->d_pb.ensure(sizeof(double) * pb.size()));
   HIP_TRY(hipMemcpy(p->d_pb.p, pb.data(), sizeof(double) * pb.size(), hipMemcpyHostToDevice));
   p->pmask = mask;
+  p->has_w = false;
   p->pb_batch = batch;
   p->version = next_version();
   return OCS_OK;
@@ -148,6 +173,8 @@ int ocs_problem_set_batch_params(ocs_problem p, int batch, const int* param_inde
 static int eval_common(ocs_problem p, int which, int k, const double* t, const double* y, const double* u,
                        const double* v, double* out) {
   if (!p || !t || !y || !u || !out || (which != 0 && !v) || k < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  if (p->has_w)
+    return fail(OCS_ERR_UNSUPPORTED, "F / dFdx_times_vec / dFdu_times_vec: per-trajectory cost weights have no meaning for k free columns");
   OCS_TRY(upload_problem(p));
   const int nAug = p->nS + 1, nC = p->nC;
   const int nout = (which == 2) ? nC : nAug;

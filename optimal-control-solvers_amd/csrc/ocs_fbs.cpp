@@ -356,7 +356,8 @@ __device__ void ocs_ControlChar(double t, const double* x, const double* lam, OC
 static int sweep_problem(ocs_problem_s* p, ocs_problem_s** out) {
   *out = p;
   if (p->functor != Functor::LQ) return OCS_OK;
-  if (p->pmask) return fail(OCS_ERR_UNSUPPORTED, "fb_sweep on the LQ problem: per-trajectory parameters are not supported");
+  // (has_w: per-trajectory cost weights -- the twin's control update reads the shared rdiag)
+  if (p->pmask || p->has_w) return fail(OCS_ERR_UNSUPPORTED, "fb_sweep on the LQ problem: per-trajectory parameters are not supported");
   // Built once: the generated source depends on (nS, nC) only, and the parameter block and bounds of a registry problem
   // never change after creation (a version bump of `p` comes from setting or clearing per-trajectory parameters, which
   // this path rejects above) -- recompiling with hipRTC on every bump cost seconds for nS = 32.  The shadow has its own
@@ -382,7 +383,7 @@ static int sweep_problem(ocs_problem_s* p, ocs_problem_s** out) {
 constexpr int kLqSweepMinStates = 8;
 static bool lq_sweep_ok(const ocs_problem_s* p, const ocs_integrator_s* g) {
   static const bool off = getenv("OCS_LQ_SWEEP") && getenv("OCS_LQ_SWEEP")[0] == '0';
-  return !off && p->functor == Functor::LQ && lq_supported(p->nS, p->nC) && !p->pmask && g->kind == 0 &&
+  return !off && p->functor == Functor::LQ && lq_supported(p->nS, p->nC) && !p->pmask && !p->has_w && g->kind == 0 &&
          p->nS >= kLqSweepMinStates;
 }
 // make sure the LQ step records of (g, p) are current (enqueued on `s`); *out: the grid with them in place of the bound problem's

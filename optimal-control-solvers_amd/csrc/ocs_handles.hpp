@@ -132,7 +132,10 @@ struct ocs_problem_s {
   std::vector<double> bounds;   // nC x 2
   DevBuf d_ps, d_pb, d_lb, d_ub;
   unsigned pmask = 0;
-  int pb_batch = 0;
+  int pb_batch = 0;             // batch of the per-trajectory parameters (d_pb under pmask, or d_w)
+  // OCS_PROBLEM_LQ only: per-trajectory cost weights [nS + nC][pb_batch] (ProblemDesc::W); never together with pmask
+  DevBuf d_w;
+  bool has_w = false;
   unsigned long long version = 0;  // bumps whenever device-visible parameters change
   bool uploaded = false;
   // OCS_PROBLEM_LQ only: the same problem as generated device source (hipRTC), built on first use by the
@@ -210,6 +213,8 @@ inline ProblemDesc describe(const ocs_problem_s* p) {
   d.ps = p->d_ps.d();
   d.pb = p->pmask ? p->d_pb.d() : nullptr;
   d.pmask = p->pmask;
+  d.W = p->has_w ? p->d_w.d() : nullptr;
+  d.Wbatch = p->has_w ? p->pb_batch : 0;
   d.lb = p->d_lb.d();
   d.ub = p->d_ub.d();
   d.user = p->user;
@@ -262,7 +267,7 @@ inline GridDesc describe(const ocs_integrator_s* g) {
 inline int bind_problem(ocs_integrator_s* g, ocs_problem_s* p, int batch, hipStream_t s) {
   OCS_TRY(upload_problem(p));
   OCS_TRY(upload_grid(g));
-  if (p->pmask && p->pb_batch != batch)
+  if ((p->pmask || p->has_w) && p->pb_batch != batch)
     return fail(OCS_ERR_SHAPE, "problem has per-trajectory parameters for batch %d, call has batch %d",
                 p->pb_batch, batch);
   if (g->tc_prob != p || g->tc_version != p->version) {

@@ -21,6 +21,11 @@ struct ProblemDesc {
   const double* ps;   // device: shared parameter block [npar]
   const double* pb;   // device: per-trajectory overrides [npar][batch] or nullptr
   unsigned pmask;     // bit k set -> parameter k is read from pb
+  // Functor::LQ only: per-trajectory cost weights [nS + nC][Wbatch] (rows 0 .. nS-1 = q, then rdiag; rows that were not
+  // overridden hold the shared block's values), or nullptr.  The parameter block of that problem has up to 1189 entries, so
+  // a mask word cannot name them; never set together with pmask.
+  const double* W = nullptr;
+  int Wbatch = 0;
   const double* lb;   // device: control lower bounds [nC]
   const double* ub;   // device: control upper bounds [nC]
   const UserModule* user = nullptr;  // set for Functor::User

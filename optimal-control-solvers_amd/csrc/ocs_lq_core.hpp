@@ -39,6 +39,9 @@ struct LQArgs {
   const double* cs;     // chunk start values [C][nS][B]: the state at the chunk's first node / the costate at its last node
   double* ce;           // CH = 1: chunk end values [C][nS][B] (state at the last node from cs / costate at the first node from 0)
   double* cj;           // CH = 2: forward: chunk objective sums [C][B]; adjoint: k1 half of the chunk's first node column [C][nC][B]
+  // per-trajectory cost weights (ocs_problem_set_batch_params on the weight range; read by the PW instantiations of the
+  // integrator passes only): [nS + nC][B], rows 0 .. nS-1 = q, rows nS .. nS+nC-1 = rdiag; null: the shared block's
+  const double* W;
 };
 
 // D = A(16x4) * B(4x16) + C on one wave; a: lane (g,i) holds A[i][g]; b: lane (g,n) holds B[g][n];
@@ -123,6 +126,12 @@ struct LQCore {
 #pragma unroll
     for (int m = 0; m < KS; ++m) q[m] = (4 * m + g < nS) ? qq[4 * m + g] : 0.0;
     R = (g < nC) ? qq[nS + g] : 0.0;
+  }
+  // q and R of trajectory b (the column this lane holds the B operand and the accumulators of) in place of the shared ones
+  __device__ inline void load_weights(const double* W, size_t B, int b, int nS, int nC, int g) {
+#pragma unroll
+    for (int m = 0; m < KS; ++m) q[m] = (4 * m + g < nS) ? W[(size_t)(4 * m + g) * B + b] : 0.0;
+    R = (g < nC) ? W[(size_t)(nS + g) * B + b] : 0.0;
   }
   // Bu * u for 16 trajectories (lane (g,n) holds u_g of trajectory n)
   __device__ inline void bu_times(double u, d4 (&o)[RT]) const {

@@ -47,7 +47,9 @@ int launch_tcoef_lq(const ProblemDesc& p, const GridDesc& g, hipStream_t s) {
 // CH (time-parallel passes, see "chunked passes" below): 0 the whole horizon from x0; 1 the chunk blockIdx.y from the
 // start state cs[c], no objective, no trajectory: only the state at the chunk's last node -> ce[c]; 2 the chunk from
 // cs[c] with every output of its steps, the running objective counted from the chunk's first node (its total -> cj[c]).
-template <int RT, bool OUT_X, bool UCONST, int CH = 0>
+// PW (every integrator pass below): q and rdiag are this lane's trajectory's own, read from a.W in the prologue
+// (ocs_problem_set_batch_params on the weight range); the time loop is the same.
+template <int RT, bool OUT_X, bool UCONST, int CH = 0, bool PW = false>
 __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
   constexpr int KS = 4 * RT;
   using Rec = StepRec<1>;
@@ -62,6 +64,7 @@ __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
 
   LQCore<RT> P;
   P.load(a.ps, nS, nC, g, n);
+  if constexpr (PW) P.load_weights(a.W, B, b, nS, nC, g);
 
   double y[KS], yc = 0.0;  // xK(:,1,1) = [x0; 0]   :33
   {
@@ -165,7 +168,7 @@ __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
 // its constant value), no outputs but the costate at the chunk's first node -> ce[c] (the part of the affine chunk map
 // lam_lo = M' lam_hi + b that does not depend on lam_hi); 2 the chunk from cs[c] with every output of its steps; the k1
 // half of its first node column of dJdu, which belongs to the column the chunk below writes, goes to cj[c].
-template <int RT, bool OUT_LAM, bool OUT_DJDU, bool UCONST, int CH = 0>
+template <int RT, bool OUT_LAM, bool OUT_DJDU, bool UCONST, int CH = 0, bool PW = false>
 __global__ __launch_bounds__(64) void k_lq_backward(const LQArgs a) {
   constexpr int KS = 4 * RT;
   using Rec = StepRec<1>;
@@ -181,6 +184,7 @@ __global__ __launch_bounds__(64) void k_lq_backward(const LQArgs a) {
 
   LQCore<RT> P;
   P.load(a.ps, nS, nC, g, n);
+  if constexpr (PW) P.load_weights(a.W, B, b, nS, nC, g);
   LQMat<RT> AT;  // fragments of A'
   load_frags<RT, true>(AT, a.ps + 1, nS, nS, nS, g, n);
   double BuT[KS];  // A-operand fragments of Bu' (nC x nS, rows padded to 16): lane (g,i) <- Bu[4 kk + g][i]
@@ -543,6 +547,12 @@ struct LQ2Core {
     for (int j = 0; j < 4; ++j) q[j] = (16 * w + 4 * j + g < nS) ? qq[16 * w + 4 * j + g] : 0.0;
     R = (w == 0 && g < nC) ? qq[nS + g] : 0.0;
   }
+  // q and R of trajectory b in place of the shared ones (LQCore::load_weights)
+  __device__ inline void load_weights(const double* W, size_t B, int b, int nS, int nC, int w, int g) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = (16 * w + 4 * j + g < nS) ? W[(size_t)(16 * w + 4 * j + g) * B + b] : 0.0;
+    R = (w == 0 && g < nC) ? W[(size_t)(nS + g) * B + b] : 0.0;
+  }
   __device__ inline d4 bu_times(double u) const {
     const d4 z = {0.0, 0.0, 0.0, 0.0};
     return mma(Bu, u, z);
@@ -555,7 +565,7 @@ struct LQ2Core {
   }
 };
 
-template <bool FULL, bool OUT_X, bool UCONST>
+template <bool FULL, bool OUT_X, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb2[2][2 * kX2Slot];
@@ -570,6 +580,7 @@ __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
   X.init(xb, w, lane);
   LQ2Core P;
   P.load(a.ps, nS, nC, w, g, n);
+  if constexpr (PW) P.load_weights(a.W, B, b, nS, nC, w, g);
 
   // own rows 16w + 4j + g, partner rows 16(1-w) + 4j + g
   double yo[4], yx[4], yc = 0.0;  // yc: this wave's share of the running cost
@@ -699,7 +710,7 @@ __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
 #endif
 }
 
-template <bool FULL, bool OUT_LAM, bool OUT_DJDU, bool UCONST>
+template <bool FULL, bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq2_backward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb2[2][2 * kX2Slot];
@@ -714,7 +725,8 @@ __global__ __launch_bounds__(256) void k_lq2_backward(const LQArgs a) {
   X.init(xb, w, lane);
   LQ2Core P;
   P.load(a.ps, nS, nC, w, g, n);
-  const double Rall = (g < nC) ? a.ps[1 + (size_t)nS * nS + (size_t)nS * nC + nS + g] : 0.0;
+  if constexpr (PW) P.load_weights(a.W, B, b, nS, nC, w, g);
+  const double Rall = (g < nC) ? (PW ? a.W[(size_t)(nS + g) * B + b] : a.ps[1 + (size_t)nS * nS + (size_t)nS * nC + nS + g]) : 0.0;
   double ATo[4], ATx[4], BuT[4];  // fragments of A' (row tile w) and of Bu' restricted to this wave's rows
   {
     const double* A = a.ps + 1;
@@ -1010,7 +1022,7 @@ __device__ static inline d4 mv4(const double (&Fr)[4], const double (&v)[4], d4 
 }
 __device__ static inline void d4_to(const d4 v, double (&f)[4]) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
 
-template <bool FULL, bool OUT_X, bool UCONST>
+template <bool FULL, bool OUT_X, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq4_forward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb[2 * kX4Slot];
@@ -1039,6 +1051,11 @@ __global__ __launch_bounds__(256) void k_lq4_forward(const LQArgs a) {
     }
     Bu = (r < nS && g < nC) ? bu[r + (size_t)nS * g] : 0.0;
     R = (wv == 0 && g < nC) ? qq[nS + g] : 0.0;   // each control's cost is counted once
+    if constexpr (PW) {   // this lane's trajectory's own weights
+#pragma unroll
+      for (int j = 0; j < 4; ++j) q[j] = (16 * h + 4 * j + g < nS) ? a.W[(size_t)(16 * h + 4 * j + g) * B + b] : 0.0;
+      R = (wv == 0 && g < nC) ? a.W[(size_t)(nS + g) * B + b] : 0.0;
+    }
   }
   auto bu_times = [&](double u) OCS_INLINE { return h == 0 ? mma(Bu, u, z4) : z4; };   // (wave-uniform)
   auto cost_part = [&](const double (&Y)[4], double u, double e) OCS_INLINE {
@@ -1170,7 +1187,7 @@ __global__ __launch_bounds__(256) void k_lq4_forward(const LQArgs a) {
   }
 }
 
-template <bool FULL, bool OUT_LAM, bool OUT_DJDU, bool UCONST>
+template <bool FULL, bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq4_backward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb[2 * kX4Slot];
@@ -1201,8 +1218,12 @@ __global__ __launch_bounds__(256) void k_lq4_backward(const LQArgs a) {
       q[j] = (16 * h + 4 * j + g < nS) ? qq[16 * h + 4 * j + g] : 0.0;
     }
     Bu = (r < nS && g < nC) ? bu[r + (size_t)nS * g] : 0.0;
+    if constexpr (PW) {   // this lane's trajectory's own weights
+#pragma unroll
+      for (int j = 0; j < 4; ++j) q[j] = (16 * h + 4 * j + g < nS) ? a.W[(size_t)(16 * h + 4 * j + g) * B + b] : 0.0;
+    }
   }
-  const double Rall = (g < nC) ? a.ps[1 + (size_t)nS * nS + (size_t)nS * nC + nS + g] : 0.0;
+  const double Rall = (g < nC) ? (PW ? a.W[(size_t)(nS + g) * B + b] : a.ps[1 + (size_t)nS * nS + (size_t)nS * nC + nS + g]) : 0.0;
   auto bu_times = [&](double u) OCS_INLINE { return h == 0 ? mma(Bu, u, z4) : z4; };
   auto but_part = [&](const double (&v)[4]) OCS_INLINE {   // (Bu' v)_g over the rows of tile h
     d4 acc = mma(BuT[0], v[0], z4), alt = mma(BuT[1], v[1], z4);
@@ -1670,7 +1691,7 @@ static int lq_chunk_matrices(LqWorkspace* w, const ProblemDesc& p, const GridDes
   return hip_rc_lq(hipGetLastError());
 }
 
-template <int RT>
+template <int RT, bool PW>
 static int lq_forward_chunked(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                               double* x, double* J, const FwdOpts& o, hipStream_t s) {
   LqWorkspace*& w = *g.lqws;
@@ -1686,9 +1707,10 @@ static int lq_forward_chunked(const ProblemDesc& p, const GridDesc& g, int batch
   if ((rc = lq_ensure(w->off, w->off_cap, (size_t)(C + 1) * B))) return rc;
   LQArgs a{};
   a.N = N; a.batch = batch; a.nS = nS; a.nC = nC; a.REC = g.REC; a.ps = p.ps;
-  a.x0 = x0; a.u = u; a.x = x; a.J = J; a.Jadd = o.Jadd; a.L = L;
+  a.x0 = x0; a.u = u; a.x = x; a.J = J; a.Jadd = o.Jadd; a.L = L; a.W = p.W;
   const dim3 grid((batch + 15) / 16, C), block(64);
-  // pass Z: every chunk from a zero state (cs of the carries is not read: zeros through a memset)
+  // pass Z: every chunk from a zero state (cs of the carries is not read: zeros through a memset); it forms no objective, so
+  // it reads no weights and is the same kernel with and without per-trajectory weights, like the chunk matrices
   if (hipMemsetAsync(w->cs, 0, (size_t)C * nS * B * sizeof(double), s) != hipSuccess) return (int)hipErrorUnknown;
   a.cs = w->cs; a.ce = w->ce;
   if (o.uconst) {
@@ -1710,15 +1732,15 @@ static int lq_forward_chunked(const ProblemDesc& p, const GridDesc& g, int batch
   }
   // pass X
   a.cj = w->cj; a.ce = nullptr;
-  if (o.uconst) k_lq_forward<RT, true, true, 2><<<grid, block, 0, s>>>(a);
-  else if (x) k_lq_forward<RT, true, false, 2><<<grid, block, 0, s>>>(a);
-  else k_lq_forward<RT, false, false, 2><<<grid, block, 0, s>>>(a);
+  if (o.uconst) k_lq_forward<RT, true, true, 2, PW><<<grid, block, 0, s>>>(a);
+  else if (x) k_lq_forward<RT, true, false, 2, PW><<<grid, block, 0, s>>>(a);
+  else k_lq_forward<RT, false, false, 2, PW><<<grid, block, 0, s>>>(a);
   k_lq_cost_prefix<<<dim3((batch + 255) / 256), dim3(256), 0, s>>>(batch, C, w->cj, w->off, o.Jadd, J);
   if (x && N > L) k_lq_cost_fix<<<dim3((batch + 255) / 256, N - L), dim3(256), 0, s>>>(batch, nS, N, L, w->off, x);
   return hip_rc_lq(hipGetLastError());
 }
 
-template <int RT>
+template <int RT, bool PW>
 static int lq_backward_chunked(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
                                const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s) {
   LqWorkspace*& w = *g.lqws;
@@ -1733,12 +1755,12 @@ static int lq_backward_chunked(const ProblemDesc& p, const GridDesc& g, int batc
   if ((rc = lq_ensure(w->cj, w->cj_cap, (size_t)C * (nC > 1 ? nC : 1) * B))) return rc;
   LQArgs a{};
   a.N = N; a.batch = batch; a.nS = nS; a.nC = nC; a.REC = g.REC; a.ps = p.ps;
-  a.xck = xck; a.u = u; a.lamT = lamT; a.L = L;
+  a.xck = xck; a.u = u; a.lamT = lamT; a.L = L; a.W = p.W;
   const dim3 grid((batch + 15) / 16, C), block(64);
-  // pass Z: the objective's share of every chunk map (zero costate at the chunk's last node)
+  // pass Z: the objective's share of every chunk map (zero costate at the chunk's last node) -- with the trajectory's own q
   a.ce = w->ce;
-  if (o.uconst) k_lq_backward<RT, false, false, true, 1><<<grid, block, 0, s>>>(a);
-  else k_lq_backward<RT, false, false, false, 1><<<grid, block, 0, s>>>(a);
+  if (o.uconst) k_lq_backward<RT, false, false, true, 1, PW><<<grid, block, 0, s>>>(a);
+  else k_lq_backward<RT, false, false, false, 1, PW><<<grid, block, 0, s>>>(a);
   // carries from the last node down; with a constant control (the tail leg of RK4InfiniteIntegrator.m:27-30) only
   // lam(:,1) is wanted, which is the carry below the first chunk
   double* last = nullptr;
@@ -1749,9 +1771,9 @@ static int lq_backward_chunked(const ProblemDesc& p, const GridDesc& g, int batc
     return hip_rc_lq(hipGetLastError());
   }
   a.ce = nullptr; a.cs = w->cs; a.cj = w->cj; a.lam = lam; a.dJdu = dJdu; a.lam0 = o.lam0;
-  if (lam && dJdu) k_lq_backward<RT, true, true, false, 2><<<grid, block, 0, s>>>(a);
-  else if (lam) k_lq_backward<RT, true, false, false, 2><<<grid, block, 0, s>>>(a);
-  else k_lq_backward<RT, false, true, false, 2><<<grid, block, 0, s>>>(a);
+  if (lam && dJdu) k_lq_backward<RT, true, true, false, 2, PW><<<grid, block, 0, s>>>(a);
+  else if (lam) k_lq_backward<RT, true, false, false, 2, PW><<<grid, block, 0, s>>>(a);
+  else k_lq_backward<RT, false, true, false, 2, PW><<<grid, block, 0, s>>>(a);
   if (dJdu && C > 1) k_lq_djdu_fix<<<dim3((batch + 255) / 256, C - 1, nC), dim3(256), 0, s>>>(batch, nC, L, C, w->cj, dJdu);
   return hip_rc_lq(hipGetLastError());
 }
@@ -1789,37 +1811,38 @@ static bool lq_four_wave(int batch, int mapping) {
   return batch <= 4096;
 }
 
-template <int RT>
+template <int RT, bool PW>
 static void run_lq_forward(const LQArgs& a, bool uconst, hipStream_t s) {
   const dim3 grid((a.batch + 15) / 16), block(64);
   if (uconst)
-    k_lq_forward<RT, true, true><<<grid, block, 0, s>>>(a);
+    k_lq_forward<RT, true, true, 0, PW><<<grid, block, 0, s>>>(a);
   else if (a.x)
-    k_lq_forward<RT, true, false><<<grid, block, 0, s>>>(a);
+    k_lq_forward<RT, true, false, 0, PW><<<grid, block, 0, s>>>(a);
   else
-    k_lq_forward<RT, false, false><<<grid, block, 0, s>>>(a);
+    k_lq_forward<RT, false, false, 0, PW><<<grid, block, 0, s>>>(a);
 }
-int launch_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
-                      double* x, double* J, const FwdOpts& o, hipStream_t s) {
-  if (!lq_supported(p.nS, p.nC) || p.pmask || o.frozen || (o.uconst && !x)) return -1;
+// PW: per-trajectory cost weights (p.W)
+template <bool PW>
+static int lq_forward_dispatch(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
+                               double* x, double* J, const FwdOpts& o, hipStream_t s) {
   LQArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
-  a.x0 = x0; a.u = u; a.x = x; a.J = J; a.Jadd = o.Jadd;
+  a.x0 = x0; a.u = u; a.x = x; a.J = J; a.Jadd = o.Jadd; a.W = p.W;
   // (a constant control -- the tail leg -- needs no pass Z of its own: the zero-start responses are one vector per chunk for
   //  the whole batch, so its chunks carry no doubled work and pay as soon as there are two of them)
   if (g.lqws && lq_chunked(batch, g.N, o.mapping, o.uconst))
-    return p.nS <= 16 ? lq_forward_chunked<1>(p, g, batch, x0, u, x, J, o, s) : lq_forward_chunked<2>(p, g, batch, x0, u, x, J, o, s);
+    return p.nS <= 16 ? lq_forward_chunked<1, PW>(p, g, batch, x0, u, x, J, o, s) : lq_forward_chunked<2, PW>(p, g, batch, x0, u, x, J, o, s);
   if (p.nS <= 16) {
-    run_lq_forward<1>(a, o.uconst, s);
+    run_lq_forward<1, PW>(a, o.uconst, s);
   } else if (lq_four_wave(batch, o.mapping)) {
     const dim3 grid((batch + 15) / 16), block(256);
     const bool fullp = p.nS == 32;
     if (o.uconst)
-      fullp ? k_lq4_forward<true, true, true><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, true, true><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq4_forward<true, true, true, PW><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, true, true, PW><<<grid, block, 0, s>>>(a);
     else if (a.x)
-      fullp ? k_lq4_forward<true, true, false><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, true, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq4_forward<true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, true, false, PW><<<grid, block, 0, s>>>(a);
     else
-      fullp ? k_lq4_forward<true, false, false><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, false, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq4_forward<true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, false, false, PW><<<grid, block, 0, s>>>(a);
   } else if (lq_two_wave(batch, o.mapping)) {
     const dim3 grid((batch + 31) / 32), block(256);
 #ifdef OCS_LQ_STAMPS
@@ -1830,11 +1853,11 @@ int launch_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const 
 #endif
     const bool fullp = p.nS == 32;
     if (o.uconst)
-      fullp ? k_lq2_forward<true, true, true><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, true, true><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq2_forward<true, true, true, PW><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, true, true, PW><<<grid, block, 0, s>>>(a);
     else if (a.x)
-      fullp ? k_lq2_forward<true, true, false><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, true, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq2_forward<true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, true, false, PW><<<grid, block, 0, s>>>(a);
     else
-      fullp ? k_lq2_forward<true, false, false><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, false, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq2_forward<true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, false, false, PW><<<grid, block, 0, s>>>(a);
 #ifdef OCS_LQ_STAMPS
     (void)hipStreamSynchronize(s);
     std::vector<long long> h(8 * grid.x);
@@ -1846,65 +1869,81 @@ int launch_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const 
             " | wave1: %.0f %.0f %.0f %.0f\n", acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7]);
 #endif
   } else {
-    run_lq_forward<2>(a, o.uconst, s);
+    run_lq_forward<2, PW>(a, o.uconst, s);
   }
   return hip_rc_lq(hipGetLastError());
 }
+// p.pmask: per-trajectory r, A or Bu -- no kernel reads them (the Jacobian is the shared A operand of the matrix instruction);
+// p.W: per-trajectory q and rdiag for exactly `p.Wbatch` trajectories
+int launch_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
+                      double* x, double* J, const FwdOpts& o, hipStream_t s) {
+  if (!lq_supported(p.nS, p.nC) || p.pmask || o.frozen || (o.uconst && !x)) return -1;
+  if (p.W && p.Wbatch != batch) return -1;
+  return p.W ? lq_forward_dispatch<true>(p, g, batch, x0, u, x, J, o, s) : lq_forward_dispatch<false>(p, g, batch, x0, u, x, J, o, s);
+}
 
-template <int RT>
+template <int RT, bool PW>
 static void run_lq_backward(const LQArgs& a, bool uconst, hipStream_t s) {
   const dim3 grid((a.batch + 15) / 16), block(64);
   if (uconst)
-    k_lq_backward<RT, false, false, true><<<grid, block, 0, s>>>(a);
+    k_lq_backward<RT, false, false, true, 0, PW><<<grid, block, 0, s>>>(a);
   else if (a.lam && a.dJdu)
-    k_lq_backward<RT, true, true, false><<<grid, block, 0, s>>>(a);
+    k_lq_backward<RT, true, true, false, 0, PW><<<grid, block, 0, s>>>(a);
   else if (a.lam)
-    k_lq_backward<RT, true, false, false><<<grid, block, 0, s>>>(a);
+    k_lq_backward<RT, true, false, false, 0, PW><<<grid, block, 0, s>>>(a);
   else
-    k_lq_backward<RT, false, true, false><<<grid, block, 0, s>>>(a);
+    k_lq_backward<RT, false, true, false, 0, PW><<<grid, block, 0, s>>>(a);
 }
-int launch_backward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
-                       const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s) {
-  if (!lq_supported(p.nS, p.nC) || p.pmask) return -1;
-  if (o.uconst ? (lam || dJdu || !o.lam0) : (!lam && !dJdu)) return -1;
+template <bool PW>
+static int lq_backward_dispatch(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
+                                const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s) {
   LQArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
-  a.xck = xck; a.u = u; a.lamT = lamT; a.lam = lam; a.dJdu = dJdu; a.lam0 = o.lam0;
+  a.xck = xck; a.u = u; a.lamT = lamT; a.lam = lam; a.dJdu = dJdu; a.lam0 = o.lam0; a.W = p.W;
   if (g.lqws && lq_chunked(batch, g.N, o.mapping, o.uconst))
-    return p.nS <= 16 ? lq_backward_chunked<1>(p, g, batch, xck, u, lamT, lam, dJdu, o, s)
-                      : lq_backward_chunked<2>(p, g, batch, xck, u, lamT, lam, dJdu, o, s);
+    return p.nS <= 16 ? lq_backward_chunked<1, PW>(p, g, batch, xck, u, lamT, lam, dJdu, o, s)
+                      : lq_backward_chunked<2, PW>(p, g, batch, xck, u, lamT, lam, dJdu, o, s);
   if (p.nS <= 16) {
-    run_lq_backward<1>(a, o.uconst, s);
+    run_lq_backward<1, PW>(a, o.uconst, s);
   } else if (lq_four_wave(batch, o.mapping)) {
     const dim3 grid((batch + 15) / 16), block(256);
     const bool fullp = p.nS == 32;
     if (o.uconst)
-      fullp ? k_lq4_backward<true, false, false, true><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, false, false, true><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq4_backward<true, false, false, true, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, false, false, true, PW><<<grid, block, 0, s>>>(a);
     else if (a.lam && a.dJdu)
-      fullp ? k_lq4_backward<true, true, true, false><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, true, true, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq4_backward<true, true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, true, true, false, PW><<<grid, block, 0, s>>>(a);
     else if (a.lam)
-      fullp ? k_lq4_backward<true, true, false, false><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, true, false, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq4_backward<true, true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, true, false, false, PW><<<grid, block, 0, s>>>(a);
     else
-      fullp ? k_lq4_backward<true, false, true, false><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, false, true, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq4_backward<true, false, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, false, true, false, PW><<<grid, block, 0, s>>>(a);
   } else if (lq_two_wave(batch, o.mapping)) {
     const dim3 grid((batch + 31) / 32), block(256);
     const bool fullp = p.nS == 32;
     if (o.uconst)
-      fullp ? k_lq2_backward<true, false, false, true><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, false, false, true><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq2_backward<true, false, false, true, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, false, false, true, PW><<<grid, block, 0, s>>>(a);
     else if (a.lam && a.dJdu)
-      fullp ? k_lq2_backward<true, true, true, false><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, true, true, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq2_backward<true, true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, true, true, false, PW><<<grid, block, 0, s>>>(a);
     else if (a.lam)
-      fullp ? k_lq2_backward<true, true, false, false><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, true, false, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq2_backward<true, true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, true, false, false, PW><<<grid, block, 0, s>>>(a);
     else
-      fullp ? k_lq2_backward<true, false, true, false><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, false, true, false><<<grid, block, 0, s>>>(a);
+      fullp ? k_lq2_backward<true, false, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, false, true, false, PW><<<grid, block, 0, s>>>(a);
   } else {
-    run_lq_backward<2>(a, o.uconst, s);
+    run_lq_backward<2, PW>(a, o.uconst, s);
   }
   return hip_rc_lq(hipGetLastError());
+}
+int launch_backward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
+                       const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s) {
+  if (!lq_supported(p.nS, p.nC) || p.pmask) return -1;
+  if (p.W && p.Wbatch != batch) return -1;
+  if (o.uconst ? (lam || dJdu || !o.lam0) : (!lam && !dJdu)) return -1;
+  return p.W ? lq_backward_dispatch<true>(p, g, batch, xck, u, lamT, lam, dJdu, o, s)
+             : lq_backward_dispatch<false>(p, g, batch, xck, u, lamT, lam, dJdu, o, s);
 }
 
 int launch_eval_lq(const ProblemDesc& p, int which, int k, const double* t, const double* y, const double* u,
                    const double* v, double* out, hipStream_t s) {
+  if (p.W) return -1;   // k free columns have no trajectory index
   k_lq_eval<<<dim3((k + 127) / 128), dim3(128), 0, s>>>(which, k, p.nS, p.nC, t, y, u, v, p.ps, out);
   return hip_rc_lq(hipGetLastError());
 }

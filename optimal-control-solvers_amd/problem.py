@@ -150,7 +150,8 @@ class LogisticProblem(OCProblem):
 class LQProblem(OCProblem):
     """Build-defined linear-quadratic problem: F = [A x + Bu u ; e^{-rt}(x'diag(q)x + u'diag(rdiag)u)].
     The Jacobian A is shared by the whole batch, so the integrator passes run on the matrix cores
-    (csrc/ocs_lq_kernels.hip).  nS <= 32, nC <= 4."""
+    (csrc/ocs_lq_kernels.hip).  nS <= 32, nC <= 4.  The cost weights q and rdiag may differ per trajectory
+    (set_batch_weights); A, Bu and r are shared."""
 
     def __init__(self, A, Bu, q, rdiag, r, ControlBounds):
         A = np.asarray(A, dtype=np.float64)
@@ -162,3 +163,26 @@ class LQProblem(OCProblem):
         self.rdiag = np.asarray(rdiag, dtype=np.float64).reshape(nC)
         par = np.concatenate([[float(r)], A.ravel(order="F"), Bu.ravel(order="F"), self.q, self.rdiag])
         super().__init__(PROBLEM_LQ, nS, nC, par, ControlBounds)
+
+    def set_batch_weights(self, q=None, rdiag=None):
+        """Per-trajectory cost weights: q is nS x batch, rdiag is nC x batch; None keeps the shared values of that
+        block, both None clears the weights.  The integrator passes and everything built on them (nlp_objective,
+        single_shooting_batch, RK4InfiniteIntegrator) then use trajectory b's own weights; fb_sweep, compute_x_lam,
+        ControlChar and the plugin methods F / dFdx_times_vec / dFdu_times_vec refuse the problem while they are set."""
+        w0 = 1 + self.nS * self.nS + self.nS * self.nC   # [r | A | Bu | q | rdiag]
+        index, rows, batch = [], [], None
+        for name, val, n, first in (("q", q, self.nS, w0), ("rdiag", rdiag, self.nC, w0 + self.nS)):
+            if val is None:
+                continue
+            val = np.asarray(val, dtype=np.float64)
+            if val.ndim != 2 or val.shape[0] != n or val.shape[1] < 1:
+                raise ValueError(f"{name} must be {n} x batch, got shape {val.shape}")
+            if batch is not None and val.shape[1] != batch:
+                raise ValueError(f"q has batch {batch}, rdiag has batch {val.shape[1]}")
+            batch = val.shape[1]
+            index.extend(range(first, first + n))
+            rows.append(val)
+        if not index:
+            self.set_batch_params([], None)
+        else:
+            self.set_batch_params(index, np.vstack(rows))
