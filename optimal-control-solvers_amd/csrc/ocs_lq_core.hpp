@@ -1,6 +1,7 @@
 // ocs_lq_core.hpp -- what the matrix-core kernels of the shared-Jacobian linear-quadratic problem have in common
-// (ocs_lq_kernels.hip: the integrator passes; ocs_lq_sweep_kernels.hip: the state and costate passes of fb_sweep):
-// the MFMA wrapper, the A-operand fragments of a matrix, the products on them and the problem's parameter block.
+// (ocs_lq_kernels.hip: the integrator passes, the one-wave state pass being fb_sweep's too; ocs_lq_sweep_kernels.hip: the
+// costate pass of fb_sweep and the launchers of both sweep passes): the MFMA wrapper, the A-operand fragments of a matrix,
+// the products on them and the problem's parameter block.
 // Mapping "M" (one wave per 16 trajectories) is described at the top of ocs_lq_kernels.hip.
 #pragma once
 #include "ocs_device_common.hpp"
@@ -8,6 +9,8 @@
 namespace ocs {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+
+static inline int hip_rc_lq(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // time coefficients of the LQ problem for the shared table builders (k_tcoef / k_build_rec)
 struct LQTime {
@@ -33,7 +36,9 @@ struct LQArgs {
   double* lam;          // [N+1][nAug][B] or null
   double* dJdu;         // [2N+1][nC][B] or null
   double* lam0;         // [nAug][B] or null
-  long long* dbg;       // diagnostic builds only: [blocks][8] cycle sums
+  // fb_sweep's state pass (k_lq_forward with SWEEP; not read by the integrator's passes)
+  const int* frozen;    // optional [B]: instances with frozen[b] != 0 store nothing
+  const int* gate;      // optional: the launch does nothing if *gate == 0
   // time-parallel passes (k_lq_forward / k_lq_backward with CH != 0): blockIdx.y = chunk c, steps [c L, min(N, (c+1) L))
   int L;                // steps per chunk
   const double* cs;     // chunk start values [C][nS][B]: the state at the chunk's first node / the costate at its last node
@@ -43,6 +48,8 @@ struct LQArgs {
   // integrator passes only): [nS + nC][B], rows 0 .. nS-1 = q, rows nS .. nS+nC-1 = rdiag; null: the shared block's
   const double* W;
 };
+// k_lq_forward<RT, true, false, 0, false, SWEEP = true> on `a`, RT by a.nS (ocs_lq_kernels.hip)
+void lq_forward_one_wave(const LQArgs& a, hipStream_t s);
 
 // D = A(16x4) * B(4x16) + C on one wave; a: lane (g,i) holds A[i][g]; b: lane (g,n) holds B[g][n];
 // c/d: lane (g,n) holds rows g + 4j of column n.

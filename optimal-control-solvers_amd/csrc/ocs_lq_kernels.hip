@@ -25,14 +25,8 @@
 #include "ocs_scan_kernel.hpp"   // Buf: raw buffer accesses with scalar offsets
 #include <cstdlib>
 #include <vector>
-#ifdef OCS_LQ_STAMPS
-#include <cstdio>
-#include <vector>
-#endif
 
 namespace ocs {
-
-static inline int hip_rc_lq(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 int launch_tcoef_lq(const ProblemDesc& p, const GridDesc& g, hipStream_t s) {
   const int nT = 2 * g.N + 1;
@@ -49,8 +43,15 @@ int launch_tcoef_lq(const ProblemDesc& p, const GridDesc& g, hipStream_t s) {
 // cs[c] with every output of its steps, the running objective counted from the chunk's first node (its total -> cj[c]).
 // PW (every integrator pass below): q and rdiag are this lane's trajectory's own, read from a.W in the prologue
 // (ocs_problem_set_batch_params on the weight range); the time loop is the same.
-template <int RT, bool OUT_X, bool UCONST, int CH = 0, bool PW = false>
+// SWEEP: fb_sweep's state pass (lq_forward_one_wave), which honours a.gate and a.frozen (ocs_lq_sweep_kernels.hip says what
+// they ask); a lane is switched off for stores by a buffer offset past num_records (kOffDrop): no branch in the recursion.
+// The integrator's instantiations do not read the two: with the tests in them the one-wave state pass at batch 16 384
+// (2 x 4000 steps) took 19.5 ms instead of 18.9, the time loop the same instructions in another order.
+template <int RT, bool OUT_X, bool UCONST, int CH = 0, bool PW = false, bool SWEEP = false>
 __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
+  if constexpr (SWEEP) {
+    if (a.gate && *a.gate == 0) return;
+  }
   constexpr int KS = 4 * RT;
   using Rec = StepRec<1>;
   const int lane = threadIdx.x, g = lane >> 4, n = lane & 15;
@@ -61,6 +62,8 @@ __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
   const size_t nAugB = (size_t)(nS + 1) * B;
   const int ch = CH ? (int)blockIdx.y : 0;
   const int i0 = CH ? ch * a.L : 0, i1 = CH ? (i0 + a.L < N ? i0 + a.L : N) : N;
+  // this lane's trajectory is stored (the integrator also stores what tail lanes recompute: the same values)
+  const bool keep = !SWEEP || (b0 < a.batch && !(a.frozen && a.frozen[b] != 0));
 
   LQCore<RT> P;
   P.load(a.ps, nS, nC, g, n);
@@ -77,8 +80,8 @@ __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
   //  the pass: no 64-bit vector address arithmetic on the pipe the matrix instructions need -- see k_lq2_forward)
   unsigned vrow[KS];
 #pragma unroll
-  for (int m = 0; m < KS; ++m) vrow[m] = (4 * m + g < nS) ? (unsigned)(((size_t)(4 * m + g) * B + b) * 8) : kOffDrop;
-  const unsigned vcost = (g == 0) ? (unsigned)(((size_t)nS * B + b) * 8) : kOffDrop;
+  for (int m = 0; m < KS; ++m) vrow[m] = (keep && 4 * m + g < nS) ? (unsigned)(((size_t)(4 * m + g) * B + b) * 8) : kOffDrop;
+  const unsigned vcost = (keep && g == 0) ? (unsigned)(((size_t)nS * B + b) * 8) : kOffDrop;
   auto store_x = [&](int col) OCS_INLINE {
     if (!OUT_X) return;
     const Buf bx = Buf::make(a.x + (size_t)col * nAugB);
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
     for (int rt = 0; rt < RT; ++rt) buA[rt] = buB[rt];
   }
   if (CH == 0) {
-    if (g == 0) a.J[b] = a.Jadd ? a.Jadd[b] + yc : yc;  // J = x(end,end)   :55
+    if (keep && g == 0) a.J[b] = a.Jadd ? a.Jadd[b] + yc : yc;  // J = x(end,end)   :55
   } else if (CH == 1) {
     double* ye = a.ce + (size_t)ch * nS * B;
 #pragma unroll
@@ -391,17 +394,10 @@ __device__ static inline void lq_lds_barrier() {
 struct LQ2Pending {
   d2 a, b, c;
 };
-// diagnostic build (-DOCS_LQ_STAMPS): cycle stamps around the phases of an exchange, summed per wave
-#ifdef OCS_LQ_STAMPS
-#define LQ_T() __builtin_amdgcn_s_memtime()
-#else
-#define LQ_T() 0LL
-#endif
 struct LQ2X {
   d2* mine;
   const d2* theirs;
   int tog;
-  long long ts[4] = {0, 0, 0, 0};  // post->barrier passed | ->own half issued | ->partner's values here | ->result read
   __device__ inline void init(d2* xb, int w, int lane) {
     mine = xb + w * kX2Wave + lane;
     theirs = xb + (1 - w) * kX2Wave + lane;
@@ -441,55 +437,24 @@ struct LQ2X {
 template <bool EXTRA, int NMID = 0, class Mid>
 __device__ static inline LQ2Pending xmv(LQ2X& X, const double (&Fo)[4], const double (&Fx)[4], const double (&vo)[4],
                                         d4 init, double (&vx)[4], double (&f)[4], double e0, double e1, Mid&& mid) {
-  const d4 z = {0.0, 0.0, 0.0, 0.0};
-  const long long t0 = LQ_T();
   X.post<EXTRA>(vo, e0, e1);
   // two products ahead of the barrier: the wave blocks on the second until the first has left the pipe
   // (~70 cycles), which is about when its LDS writes have landed; the other two cover the read latency
-#ifndef OCS_LQ_TWO_CHAINS
   // One accumulation chain: a dependent v_mfma_f64_16x16x4_f64 issues as soon as its predecessor leaves the pipe, so two
   // chains gain nothing and their final addition (4 v_add_f64 behind the last result) only lengthens the stage's tail:
   // state pass 11.79 -> 11.44 ms, adjoint 20.13 -> 19.77 ms at BL-5.
-  (void)z;
   d4 acc = mma(Fo[0], vo[0], init);
   acc = mma(Fo[1], vo[1], acc);
   const LQ2Pending r = X.sync<EXTRA>();
-  const long long t1 = LQ_T();
   acc = mma(Fo[2], vo[2], acc);
   acc = mma(Fo[3], vo[3], acc);
-#else
-  d4 acc = mma(Fo[0], vo[0], init);
-  d4 alt = mma(Fo[1], vo[1], z);
-  const LQ2Pending r = X.sync<EXTRA>();
-  const long long t1 = LQ_T();
-  acc = mma(Fo[2], vo[2], acc);
-  alt = mma(Fo[3], vo[3], alt);
-#endif
   mid();
-#ifdef OCS_LQ_STAMPS
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-  const long long t2 = LQ_T();
   LQ2X::take(r, vx);
-#ifdef OCS_LQ_STAMPS
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-  const long long t3 = LQ_T();
-#ifndef OCS_LQ_TWO_CHAINS
   acc = mma(Fx[0], vx[0], acc);
   acc = mma(Fx[1], vx[1], acc);
   acc = mma(Fx[2], vx[2], acc);
   acc = mma(Fx[3], vx[3], acc);
-#else
-  acc = mma(Fx[0], vx[0], acc);
-  alt = mma(Fx[1], vx[1], alt);
-  acc = mma(Fx[2], vx[2], acc);
-  alt = mma(Fx[3], vx[3], alt);
-  acc += alt;
-#endif
   f[0] = acc.x; f[1] = acc.y; f[2] = acc.z; f[3] = acc.w;
-#ifndef OCS_LQ_STAMPS
   // Issue order of this region (from the barrier to the next post): one matrix instruction, then a few of the
   // independent vector / memory instructions (`mid`, address arithmetic, the step's loads and stores), and so
   // on.  A wave issues in order and blocks on a matrix instruction while the pipe is busy (~70 cycles), so
@@ -500,16 +465,6 @@ __device__ static inline LQ2Pending xmv(LQ2X& X, const double (&Fo)[4], const do
     __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // VALU
     __builtin_amdgcn_sched_group_barrier(0x060, 2, 0);  // VMEM read / write
   }
-#endif
-#ifdef OCS_LQ_STAMPS
-  asm volatile("" ::"v"(f[0]), "v"(f[1]), "v"(f[2]), "v"(f[3]));
-  __builtin_amdgcn_sched_barrier(0);
-  const long long t4 = LQ_T();
-  X.ts[0] += t1 - t0;
-  X.ts[1] += t2 - t1;
-  X.ts[2] += t3 - t2;
-  X.ts[3] += t4 - t3;
-#endif
   return r;
 }
 // the same product when both halves are already known (no exchange)
@@ -565,7 +520,7 @@ struct LQ2Core {
   }
 };
 
-template <bool FULL, bool OUT_X, bool UCONST, bool PW = false>
+template <bool OUT_X, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb2[2][2 * kX2Slot];
@@ -593,11 +548,10 @@ __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
   // Outputs and control samples go through raw buffer descriptors rebuilt per step on the scalar unit (base of the
   // column) with a per-lane byte offset fixed for the whole pass: 64-bit pointer arithmetic per access was ~36 vector
   // instructions per step, on the pipe the matrix instructions need.
-  const unsigned B8 = (unsigned)(B * 8);
   unsigned vrow[4];   // byte offset of row 16w + 4j + g of this lane's trajectory inside a column (dropped if padded)
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    vrow[j] = (FULL || 16 * w + 4 * j + g < nS) ? (unsigned)(((size_t)(16 * w + 4 * j + g) * B + b) * 8) : kOffDrop;
+    vrow[j] = (16 * w + 4 * j + g < nS) ? (unsigned)(((size_t)(16 * w + 4 * j + g) * B + b) * 8) : kOffDrop;
   const unsigned vcost = (w == 0 && g == 0) ? (unsigned)(((size_t)nS * B + b) * 8) : kOffDrop;
   if (OUT_X) {
     const Buf bx0 = Buf::make(a.x);
@@ -619,7 +573,6 @@ __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
   d4 buA = P.bu_times(uA), buM = buA, buB = buA;
   double F1[4];
   mv2(P.Ao, P.Ax, yo, yx, buA, F1);  // stage 1 of step 0 (later steps: under the y exchange of the step before)
-  auto nothing = []() {};
 
   // Per-step inputs (uniform record, two control samples) are requested TWO steps ahead into two slots that the
   // steps use alternately.  vmcnt counts loads and stores in order, so with a lead of one step the wait for
@@ -704,13 +657,9 @@ __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
       a.J[b] = a.Jadd ? a.Jadd[b] + Jt : Jt;  // J = x(end,end)   :55
     }
   }
-#ifdef OCS_LQ_STAMPS
-  if (a.dbg && lane == 0 && pair == 0)
-    for (int k = 0; k < 4; ++k) a.dbg[blockIdx.x * 8 + w * 4 + k] = X.ts[k];
-#endif
 }
 
-template <bool FULL, bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW = false>
+template <bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq2_backward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb2[2][2 * kX2Slot];
@@ -765,8 +714,8 @@ __global__ __launch_bounds__(256) void k_lq2_backward(const LQArgs a) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int ro = 16 * w + 4 * j + g, rx = 16 * (1 - w) + 4 * j + g;
-    vown[j] = (FULL || ro < nS) ? (unsigned)(((size_t)ro * B + b) * 8) : kOffDrop;
-    vpar[j] = (FULL || rx < nS) ? (unsigned)(((size_t)rx * B + b) * 8) : kOffDrop;
+    vown[j] = (ro < nS) ? (unsigned)(((size_t)ro * B + b) * 8) : kOffDrop;
+    vpar[j] = (rx < nS) ? (unsigned)(((size_t)rx * B + b) * 8) : kOffDrop;
   }
   const unsigned vlamc = (w == 0 && g == 0) ? (unsigned)(((size_t)nS * B + b) * 8) : kOffDrop;
   auto store_lam = [&](int col) OCS_INLINE {
@@ -1022,7 +971,7 @@ __device__ static inline d4 mv4(const double (&Fr)[4], const double (&v)[4], d4 
 }
 __device__ static inline void d4_to(const d4 v, double (&f)[4]) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
 
-template <bool FULL, bool OUT_X, bool UCONST, bool PW = false>
+template <bool OUT_X, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq4_forward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb[2 * kX4Slot];
@@ -1077,7 +1026,7 @@ __global__ __launch_bounds__(256) void k_lq4_forward(const LQArgs a) {
   unsigned vrow[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    vrow[j] = (storew && (FULL || 16 * h + 4 * j + g < nS)) ? (unsigned)(((size_t)(16 * h + 4 * j + g) * B + b) * 8) : kOffDrop;
+    vrow[j] = (storew && 16 * h + 4 * j + g < nS) ? (unsigned)(((size_t)(16 * h + 4 * j + g) * B + b) * 8) : kOffDrop;
   const unsigned vcost = (wv == 0 && g == 0) ? (unsigned)(((size_t)nS * B + b) * 8) : kOffDrop;
   if (OUT_X) {
     const Buf bx0 = Buf::make(a.x);
@@ -1187,7 +1136,7 @@ __global__ __launch_bounds__(256) void k_lq4_forward(const LQArgs a) {
   }
 }
 
-template <bool FULL, bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW = false>
+template <bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW = false>
 __global__ __launch_bounds__(256) void k_lq4_backward(const LQArgs a) {
   using Rec = StepRec<1>;
   __shared__ d2 xb[2 * kX4Slot];
@@ -1249,7 +1198,7 @@ __global__ __launch_bounds__(256) void k_lq4_backward(const LQArgs a) {
   unsigned vrow[4], vst[4];   // rows of tile h of this lane's trajectory: loads (every wave), stores (waves (1, h))
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    vrow[j] = (FULL || 16 * h + 4 * j + g < nS) ? (unsigned)(((size_t)(16 * h + 4 * j + g) * B + b) * 8) : kOffDrop;
+    vrow[j] = (16 * h + 4 * j + g < nS) ? (unsigned)(((size_t)(16 * h + 4 * j + g) * B + b) * 8) : kOffDrop;
     vst[j] = storew ? vrow[j] : kOffDrop;
   }
   const unsigned vlamc = (wv == 2 && g == 0) ? (unsigned)(((size_t)nS * B + b) * 8) : kOffDrop;
@@ -1624,17 +1573,18 @@ __global__ void k_lq_set_row(int B, double* __restrict__ dst, const double* __re
   if (b < B) dst[b] = src ? src[b] : 1.0;
 }
 
-// how many chunks: groups x C = 2048 waves, two per SIMD (measured at 1024 trajectories, 2 x 4000 steps, pass pair: 1024 waves
-// 7.8 ms, 2048 6.6 ms, 4096 6.6 ms; the X passes hold at most two waves per SIMD in registers); at most 64 chunks; chunks of
-// at least 32 steps when chosen automatically (2 when the mapping is requested: tests, tuning).  OCS_LQ_CHUNK_WAVES
-// overrides the wave target.
-static bool lq_chunk_forced(int mapping) {
+static int lq_env_map() {
   static const int env = [] {
     const char* e = getenv("OCS_LQ_MAP");
     return e ? atoi(e) : 0;
   }();
-  return mapping == MAP_SCAN || (mapping == MAP_AUTO && env == 5);
+  return env;
 }
+// how many chunks: groups x C = 2048 waves, two per SIMD (measured at 1024 trajectories, 2 x 4000 steps, pass pair: 1024 waves
+// 7.8 ms, 2048 6.6 ms, 4096 6.6 ms; the X passes hold at most two waves per SIMD in registers); at most 64 chunks; chunks of
+// at least 32 steps when chosen automatically (2 when the mapping is requested: tests, tuning).  OCS_LQ_CHUNK_WAVES
+// overrides the wave target.
+static bool lq_chunk_forced(int mapping) { return mapping == MAP_SCAN || (mapping == MAP_AUTO && lq_env_map() == 5); }
 static int lq_chunks(int batch, int N, int mapping) {
   static const int target = [] {
     const char* e = getenv("OCS_LQ_CHUNK_WAVES");
@@ -1646,21 +1596,6 @@ static int lq_chunks(int batch, int N, int mapping) {
   if (C > 64) C = 64;
   if (C > N / minlen) C = N / minlen;
   return C < 2 ? 1 : C;
-}
-// automatic selection: up to 4096 trajectories (C >= 8).  Measured, nS = 32, nC = 4, 2 x 4000 steps, pass pair: 1024 trajectories
-// 6.6 ms (four-wave kernels 28.5), 2048: ~12 (28.6), 4096: 21-23 (28.6); at 8192 the doubled work costs what the shorter chains
-// gain (two-wave kernels 30.3 ms)
-// z_only: the pass wants nothing but the value at the far end of the horizon (the adjoint of the tail leg of
-// RK4InfiniteIntegrator.m:27-30: lam2(:,1)) -- pass Z and the carries ARE that pass, there is no pass X and no doubled work, so
-// chunks pay as soon as there are two of them (8192 trajectories: 4 chunks, 2048 one-wave groups instead of 1024 exchanging pairs)
-static bool lq_chunked(int batch, int N, int mapping, bool z_only = false) {
-  static const int env = [] {
-    const char* e = getenv("OCS_LQ_MAP");
-    return e ? atoi(e) : 0;
-  }();
-  if (lq_chunk_forced(mapping)) return lq_chunks(batch, N, mapping) >= 2;
-  if (mapping != MAP_AUTO || env != 0) return false;
-  return lq_chunks(batch, N, mapping) >= (z_only ? 2 : 8);
 }
 
 template <int RT>
@@ -1782,16 +1717,16 @@ static int lq_backward_chunked(const ProblemDesc& p, const GridDesc& g, int batc
 // launchers
 // ---------------------------------------------------------------------------------------
 bool lq_supported(int nS, int nC) { return nS >= 1 && nS <= 32 && nC >= 1 && nC <= 4; }
-// mapping request (ocs_integrator_set_mapping): 1 = one wave per 16 trajectories, 2 = two waves; automatic: two
-// waves while that still leaves at most one wave per SIMD (1024 waves), one wave beyond
-static bool lq_two_wave(int batch, int mapping) {
-  if (mapping == MAP_LANE) return false;
-  if (mapping == MAP_ROWSPLIT) return true;
-  return batch <= 8192;  // beyond one wave per SIMD the single-wave mapping has less overhead
-}
-// four waves per 16 trajectories (K-split): OCS_LQ_MAP=4 always, =2 never (A/B timing); mapping request 3 forces it.
-// Automatic: while the four waves of a group still find SIMDs of their own (<= 4096 trajectories = 1024 waves).  Measured,
-// nS = 32, nC = 4, 2 x 4000 steps, ms state pass / adjoint pass, two waves -> four waves:
+// Which mapping a pass takes; m: the request (ocs_integrator_set_mapping), E: OCS_LQ_MAP (A/B timing).
+// Chunks, automatic: up to 4096 trajectories (C >= 8).  Measured, nS = 32, nC = 4, 2 x 4000 steps, pass pair: 1024 trajectories
+// 6.6 ms (four-wave kernels 28.5), 2048: ~12 (28.6), 4096: 21-23 (28.6); at 8192 the doubled work costs what the shorter chains
+// gain (two-wave kernels 30.3 ms).  uconst (the tail leg of RK4InfiniteIntegrator.m:20-30): the state pass needs no pass Z of
+// its own (the zero-start responses are one vector per chunk for the whole batch) and the adjoint wants nothing but lam2(:,1),
+// the value at the far end of the horizon -- pass Z and the carries ARE that pass, there is no pass X; no doubled work, so
+// chunks pay as soon as there are two of them (8192 trajectories: 4 chunks, 2048 one-wave groups instead of 1024 exchanging pairs).
+// Four waves per 16 trajectories (K-split): E = 4 always, E = 2 never; request 3 forces it.  Automatic: while the four waves
+// of a group still find SIMDs of their own (<= 4096 trajectories = 1024 waves).  Measured, nS = 32, nC = 4, 2 x 4000 steps, ms
+// state pass / adjoint pass, two waves -> four waves:
 //   batch 1024: 11.61 / 19.93 -> 11.02 / 18.08    2048: 11.61 / 19.99 -> 11.01 / 18.11    4096: 11.63 / 19.96 -> 11.12 / 18.26
 //   8192 (two waves of different groups per SIMD): 11.77 / 20.04 -> 16.80 / 32.88
 // A stage of M4 is 4 dependent matrix instructions + one LDS exchange of ~580 cycles that nothing of the same group can
@@ -1801,77 +1736,77 @@ static bool lq_two_wave(int batch, int mapping) {
 // latency of the last matrix instruction + the stage's vector update, ~200 of 730 cycles): with one independent wave per
 // SIMD there is nothing to fill it with; the one-wave mapping at batch 16 384 (no exchange, one wave per SIMD) runs the
 // adjoint pass at 58.6 TFLOP/s = 0.75 of the nominal peak.
-static bool lq_four_wave(int batch, int mapping) {
-  static const int env = [] {
-    const char* e = getenv("OCS_LQ_MAP");
-    return e ? atoi(e) : 0;
-  }();
-  if (mapping == MAP_LANE || mapping == MAP_ROWSPLIT || env == 2) return false;   // (MAP_ROWSPLIT: the two-wave mapping)
-  if (mapping == MAP_PIPELINE || env == 4) return true;
-  return batch <= 4096;
+// Two waves: request 2; automatic while that still leaves at most one wave per SIMD (1024 waves); beyond, the single-wave
+// mapping has less overhead.
+enum class LqMap { OneWave, TwoWaves, FourWaves, Chunks };
+static LqMap lq_mapping(const GridDesc& g, int nS, int batch, int m, bool uconst) {
+  const int E = lq_env_map();
+  if (g.lqws) {
+    if (lq_chunk_forced(m)) {
+      if (lq_chunks(batch, g.N, m) >= 2) return LqMap::Chunks;
+    } else if (m == MAP_AUTO && E == 0 && lq_chunks(batch, g.N, m) >= (uconst ? 2 : 8)) {
+      return LqMap::Chunks;
+    }
+  }
+  if (nS <= 16) return LqMap::OneWave;
+  if (!(m == MAP_LANE || m == MAP_ROWSPLIT || E == 2) && (m == MAP_PIPELINE || E == 4 || batch <= 4096)) return LqMap::FourWaves;
+  if (m != MAP_LANE && (m == MAP_ROWSPLIT || batch <= 8192)) return LqMap::TwoWaves;
+  return LqMap::OneWave;
 }
 
-template <int RT, bool PW>
+// the kernel families: trajectories and threads per workgroup, the instantiation of a pass for an output variant
+template <int RT>
+struct LqM1 {
+  static constexpr int traj = 16, threads = 64;
+  template <bool OUT_X, bool UCONST, bool PW> static constexpr auto forward = k_lq_forward<RT, OUT_X, UCONST, 0, PW>;
+  template <bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW> static constexpr auto backward = k_lq_backward<RT, OUT_LAM, OUT_DJDU, UCONST, 0, PW>;
+};
+struct LqM2 {
+  static constexpr int traj = 32, threads = 256;
+  template <bool OUT_X, bool UCONST, bool PW> static constexpr auto forward = k_lq2_forward<OUT_X, UCONST, PW>;
+  template <bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW> static constexpr auto backward = k_lq2_backward<OUT_LAM, OUT_DJDU, UCONST, PW>;
+};
+struct LqM4 {
+  static constexpr int traj = 16, threads = 256;
+  template <bool OUT_X, bool UCONST, bool PW> static constexpr auto forward = k_lq4_forward<OUT_X, UCONST, PW>;
+  template <bool OUT_LAM, bool OUT_DJDU, bool UCONST, bool PW> static constexpr auto backward = k_lq4_backward<OUT_LAM, OUT_DJDU, UCONST, PW>;
+};
+
+// K: the kernel family; PW: per-trajectory cost weights (p.W)
+template <class K, bool PW>
 static void run_lq_forward(const LQArgs& a, bool uconst, hipStream_t s) {
-  const dim3 grid((a.batch + 15) / 16), block(64);
+  const dim3 grid((a.batch + K::traj - 1) / K::traj), block(K::threads);
   if (uconst)
-    k_lq_forward<RT, true, true, 0, PW><<<grid, block, 0, s>>>(a);
+    K::template forward<true, true, PW><<<grid, block, 0, s>>>(a);
   else if (a.x)
-    k_lq_forward<RT, true, false, 0, PW><<<grid, block, 0, s>>>(a);
+    K::template forward<true, false, PW><<<grid, block, 0, s>>>(a);
   else
-    k_lq_forward<RT, false, false, 0, PW><<<grid, block, 0, s>>>(a);
+    K::template forward<false, false, PW><<<grid, block, 0, s>>>(a);
 }
-// PW: per-trajectory cost weights (p.W)
 template <bool PW>
 static int lq_forward_dispatch(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                                double* x, double* J, const FwdOpts& o, hipStream_t s) {
   LQArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
   a.x0 = x0; a.u = u; a.x = x; a.J = J; a.Jadd = o.Jadd; a.W = p.W;
-  // (a constant control -- the tail leg -- needs no pass Z of its own: the zero-start responses are one vector per chunk for
-  //  the whole batch, so its chunks carry no doubled work and pay as soon as there are two of them)
-  if (g.lqws && lq_chunked(batch, g.N, o.mapping, o.uconst))
-    return p.nS <= 16 ? lq_forward_chunked<1, PW>(p, g, batch, x0, u, x, J, o, s) : lq_forward_chunked<2, PW>(p, g, batch, x0, u, x, J, o, s);
-  if (p.nS <= 16) {
-    run_lq_forward<1, PW>(a, o.uconst, s);
-  } else if (lq_four_wave(batch, o.mapping)) {
-    const dim3 grid((batch + 15) / 16), block(256);
-    const bool fullp = p.nS == 32;
-    if (o.uconst)
-      fullp ? k_lq4_forward<true, true, true, PW><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, true, true, PW><<<grid, block, 0, s>>>(a);
-    else if (a.x)
-      fullp ? k_lq4_forward<true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, true, false, PW><<<grid, block, 0, s>>>(a);
-    else
-      fullp ? k_lq4_forward<true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_forward<false, false, false, PW><<<grid, block, 0, s>>>(a);
-  } else if (lq_two_wave(batch, o.mapping)) {
-    const dim3 grid((batch + 31) / 32), block(256);
-#ifdef OCS_LQ_STAMPS
-    static long long* dbg = nullptr;
-    if (!dbg) (void)hipMalloc((void**)&dbg, sizeof(long long) * 8 * 65536);
-    (void)hipMemsetAsync(dbg, 0, sizeof(long long) * 8 * grid.x, s);
-    a.dbg = dbg;
-#endif
-    const bool fullp = p.nS == 32;
-    if (o.uconst)
-      fullp ? k_lq2_forward<true, true, true, PW><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, true, true, PW><<<grid, block, 0, s>>>(a);
-    else if (a.x)
-      fullp ? k_lq2_forward<true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, true, false, PW><<<grid, block, 0, s>>>(a);
-    else
-      fullp ? k_lq2_forward<true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_forward<false, false, false, PW><<<grid, block, 0, s>>>(a);
-#ifdef OCS_LQ_STAMPS
-    (void)hipStreamSynchronize(s);
-    std::vector<long long> h(8 * grid.x);
-    (void)hipMemcpy(h.data(), dbg, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
-    double acc[8] = {0};
-    for (unsigned q = 0; q < grid.x; ++q)
-      for (int k = 0; k < 8; ++k) acc[k] += (double)h[8 * q + k] / grid.x / ((double)g.N * 4);
-    fprintf(stderr, "[lq2 fwd] cycles per exchange, wave0: post->barrier %.0f, own half %.0f, wait partner %.0f, partner half+read %.0f"
-            " | wave1: %.0f %.0f %.0f %.0f\n", acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7]);
-#endif
-  } else {
-    run_lq_forward<2, PW>(a, o.uconst, s);
+  switch (lq_mapping(g, p.nS, batch, o.mapping, o.uconst)) {
+    case LqMap::Chunks:
+      return p.nS <= 16 ? lq_forward_chunked<1, PW>(p, g, batch, x0, u, x, J, o, s) : lq_forward_chunked<2, PW>(p, g, batch, x0, u, x, J, o, s);
+    case LqMap::OneWave:
+      p.nS <= 16 ? run_lq_forward<LqM1<1>, PW>(a, o.uconst, s) : run_lq_forward<LqM1<2>, PW>(a, o.uconst, s);
+      break;
+    case LqMap::TwoWaves: run_lq_forward<LqM2, PW>(a, o.uconst, s); break;
+    case LqMap::FourWaves: run_lq_forward<LqM4, PW>(a, o.uconst, s); break;
   }
   return hip_rc_lq(hipGetLastError());
+}
+// fb_sweep's state pass (launch_sweep_forward_lq): the one-wave pass with every output, SWEEP
+void lq_forward_one_wave(const LQArgs& a, hipStream_t s) {
+  const dim3 grid((a.batch + 15) / 16), block(64);
+  if (a.nS <= 16)
+    k_lq_forward<1, true, false, 0, false, true><<<grid, block, 0, s>>>(a);
+  else
+    k_lq_forward<2, true, false, 0, false, true><<<grid, block, 0, s>>>(a);
 }
 // p.pmask: per-trajectory r, A or Bu -- no kernel reads them (the Jacobian is the shared A operand of the matrix instruction);
 // p.W: per-trajectory q and rdiag for exactly `p.Wbatch` trajectories
@@ -1882,17 +1817,17 @@ int launch_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const 
   return p.W ? lq_forward_dispatch<true>(p, g, batch, x0, u, x, J, o, s) : lq_forward_dispatch<false>(p, g, batch, x0, u, x, J, o, s);
 }
 
-template <int RT, bool PW>
+template <class K, bool PW>
 static void run_lq_backward(const LQArgs& a, bool uconst, hipStream_t s) {
-  const dim3 grid((a.batch + 15) / 16), block(64);
+  const dim3 grid((a.batch + K::traj - 1) / K::traj), block(K::threads);
   if (uconst)
-    k_lq_backward<RT, false, false, true, 0, PW><<<grid, block, 0, s>>>(a);
+    K::template backward<false, false, true, PW><<<grid, block, 0, s>>>(a);
   else if (a.lam && a.dJdu)
-    k_lq_backward<RT, true, true, false, 0, PW><<<grid, block, 0, s>>>(a);
+    K::template backward<true, true, false, PW><<<grid, block, 0, s>>>(a);
   else if (a.lam)
-    k_lq_backward<RT, true, false, false, 0, PW><<<grid, block, 0, s>>>(a);
+    K::template backward<true, false, false, PW><<<grid, block, 0, s>>>(a);
   else
-    k_lq_backward<RT, false, true, false, 0, PW><<<grid, block, 0, s>>>(a);
+    K::template backward<false, true, false, PW><<<grid, block, 0, s>>>(a);
 }
 template <bool PW>
 static int lq_backward_dispatch(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
@@ -1900,35 +1835,15 @@ static int lq_backward_dispatch(const ProblemDesc& p, const GridDesc& g, int bat
   LQArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
   a.xck = xck; a.u = u; a.lamT = lamT; a.lam = lam; a.dJdu = dJdu; a.lam0 = o.lam0; a.W = p.W;
-  if (g.lqws && lq_chunked(batch, g.N, o.mapping, o.uconst))
-    return p.nS <= 16 ? lq_backward_chunked<1, PW>(p, g, batch, xck, u, lamT, lam, dJdu, o, s)
-                      : lq_backward_chunked<2, PW>(p, g, batch, xck, u, lamT, lam, dJdu, o, s);
-  if (p.nS <= 16) {
-    run_lq_backward<1, PW>(a, o.uconst, s);
-  } else if (lq_four_wave(batch, o.mapping)) {
-    const dim3 grid((batch + 15) / 16), block(256);
-    const bool fullp = p.nS == 32;
-    if (o.uconst)
-      fullp ? k_lq4_backward<true, false, false, true, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, false, false, true, PW><<<grid, block, 0, s>>>(a);
-    else if (a.lam && a.dJdu)
-      fullp ? k_lq4_backward<true, true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, true, true, false, PW><<<grid, block, 0, s>>>(a);
-    else if (a.lam)
-      fullp ? k_lq4_backward<true, true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, true, false, false, PW><<<grid, block, 0, s>>>(a);
-    else
-      fullp ? k_lq4_backward<true, false, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq4_backward<false, false, true, false, PW><<<grid, block, 0, s>>>(a);
-  } else if (lq_two_wave(batch, o.mapping)) {
-    const dim3 grid((batch + 31) / 32), block(256);
-    const bool fullp = p.nS == 32;
-    if (o.uconst)
-      fullp ? k_lq2_backward<true, false, false, true, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, false, false, true, PW><<<grid, block, 0, s>>>(a);
-    else if (a.lam && a.dJdu)
-      fullp ? k_lq2_backward<true, true, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, true, true, false, PW><<<grid, block, 0, s>>>(a);
-    else if (a.lam)
-      fullp ? k_lq2_backward<true, true, false, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, true, false, false, PW><<<grid, block, 0, s>>>(a);
-    else
-      fullp ? k_lq2_backward<true, false, true, false, PW><<<grid, block, 0, s>>>(a) : k_lq2_backward<false, false, true, false, PW><<<grid, block, 0, s>>>(a);
-  } else {
-    run_lq_backward<2, PW>(a, o.uconst, s);
+  switch (lq_mapping(g, p.nS, batch, o.mapping, o.uconst)) {
+    case LqMap::Chunks:
+      return p.nS <= 16 ? lq_backward_chunked<1, PW>(p, g, batch, xck, u, lamT, lam, dJdu, o, s)
+                        : lq_backward_chunked<2, PW>(p, g, batch, xck, u, lamT, lam, dJdu, o, s);
+    case LqMap::OneWave:
+      p.nS <= 16 ? run_lq_backward<LqM1<1>, PW>(a, o.uconst, s) : run_lq_backward<LqM1<2>, PW>(a, o.uconst, s);
+      break;
+    case LqMap::TwoWaves: run_lq_backward<LqM2, PW>(a, o.uconst, s); break;
+    case LqMap::FourWaves: run_lq_backward<LqM4, PW>(a, o.uconst, s); break;
   }
   return hip_rc_lq(hipGetLastError());
 }

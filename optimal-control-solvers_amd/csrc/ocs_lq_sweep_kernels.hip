@@ -1,10 +1,12 @@
-// ocs_lq_sweep_kernels.hip -- the state pass and the costate pass of the forward-backward sweep (functions/fb_sweep.m,
-// compute_x_lam.m) for the build-defined LQ problem on the gfx950 matrix cores.
+// ocs_lq_sweep_kernels.hip -- the costate pass of the forward-backward sweep (functions/fb_sweep.m, compute_x_lam.m) for the
+// build-defined LQ problem on the gfx950 matrix cores, and the launchers of both of the sweep's passes.  Its state pass is
+// the integrator's one-wave kernel, k_lq_forward<RT, true, false> of ocs_lq_kernels.hip (compute_x_lam_J.m:6-15 on the grid
+// is RK4Integrator.m:28-56), in the instantiation that honours the sweep's frozen and gate (SWEEP).
 //
 // Mapping "M" of ocs_lq_kernels.hip: one wave per 16 trajectories, lane (g, n) = (lane >> 4, lane & 15) owns rows
-// {4m + g} of trajectory n for the whole pass; A (state pass) / A' (costate pass) sit in registers as A-operand
-// fragments of v_mfma_f64_16x16x4_f64, the stage vector is the B operand, and the C/D layout of one product is the
-// B-operand layout of the next.  RT = 1 row tile for nS <= 16, RT = 2 for nS <= 32.
+// {4m + g} of trajectory n for the whole pass; A' sits in registers as A-operand fragments of v_mfma_f64_16x16x4_f64, the
+// stage vector is the B operand, and the C/D layout of one product is the B-operand layout of the next.  RT = 1 row tile
+// for nS <= 16, RT = 2 for nS <= 32.
 //
 // What the sweep asks of a pass beyond the integrator's: a device gate (a sweep enqueued ahead of the host's knowledge
 // that the one before it left no instance active does nothing), and frozen instances (converged in an earlier sweep:
@@ -24,102 +26,13 @@ struct LQSweepArgs {
   int N, batch, nS, nC;
   const double* REC;     // StepRec<1> records of the LQ problem: e^{-rt} at A / M / B
   const double* ps;      // [r | A nS x nS col-major | Bu nS x nC | q nS | rdiag nC]
-  const double* x0;      // state pass: [nS][B]
-  const double* u;       // state pass: [2N+1][nC][B]
-  double* x;             // state pass out / costate pass in: [N+1][ldx][B]
+  const double* x;       // [N+1][ldx][B]
   int ldx;               // rows per column of x (nS + 1)
-  double* J;             // state pass out [B]
-  const double* xmid;    // costate pass: pchip midpoints of x [N][nS][B] (launch_pchip_mid)
-  double* lam;           // costate pass out [N+1][nS][B]
+  const double* xmid;    // pchip midpoints of x [N][nS][B] (launch_pchip_mid)
+  double* lam;           // out [N+1][nS][B]
   const int* frozen;     // optional [B]: instances with frozen[b] != 0 store nothing
   const int* gate;       // optional: the launch does nothing if *gate == 0
 };
-
-// ---------------------------------------------------------------------------------------
-// state pass   compute_x_lam_J.m:6-15 on the grid (RK4Integrator.m:28-56): the recursion of k_lq_forward
-// ---------------------------------------------------------------------------------------
-template <int RT>
-__global__ __launch_bounds__(64) void k_lq_sweep_forward(const LQSweepArgs a) {
-  if (a.gate && *a.gate == 0) return;
-  constexpr int KS = 4 * RT;
-  using Rec = StepRec<1>;
-  const int lane = threadIdx.x, g = lane >> 4, n = lane & 15;
-  const int b0 = blockIdx.x * 16 + n;
-  const int b = b0 < a.batch ? b0 : a.batch - 1;  // lanes past the batch recompute the last trajectory
-  const size_t B = (size_t)a.batch;
-  const int nS = a.nS, nC = a.nC, N = a.N;
-  const size_t nAugB = (size_t)a.ldx * B;
-  const bool keep = b0 < a.batch && !(a.frozen && a.frozen[b] != 0);  // this lane's trajectory is stored
-
-  LQCore<RT> P;
-  P.load(a.ps, nS, nC, g, n);
-
-  double y[KS], yc = 0.0;  // xK(:,1,1) = [x0; 0]   :33
-#pragma unroll
-  for (int m = 0; m < KS; ++m) y[m] = (4 * m + g < nS) ? a.x0[(size_t)(4 * m + g) * B + b] : 0.0;
-
-  unsigned vrow[KS];
-#pragma unroll
-  for (int m = 0; m < KS; ++m) vrow[m] = (keep && 4 * m + g < nS) ? (unsigned)(((size_t)(4 * m + g) * B + b) * 8) : kOffDrop;
-  const unsigned vcost = (keep && g == 0) ? (unsigned)(((size_t)nS * B + b) * 8) : kOffDrop;
-  auto store_x = [&](int col) OCS_INLINE {
-    const Buf bx = Buf::make(a.x + (size_t)col * nAugB);
-#pragma unroll
-    for (int m = 0; m < KS; ++m) bx.st0(y[m], vrow[m], 0);
-    bx.st0(yc, vcost, 0);
-  };
-  store_x(0);
-
-  const bool uact = g < nC;
-  const size_t ustride = (size_t)nC * B;
-  const double* up = a.u + (size_t)(uact ? g : 0) * B + b;  // u(:, 1) of this lane's control row
-  const unsigned vu = (unsigned)(((size_t)(uact ? g : 0) * B + b) * 8), us8 = (unsigned)(ustride * 8);
-  double uA = uact ? up[0] : 0.0, uM = uact ? up[ustride] : 0.0, uB = uact ? up[2 * ustride] : 0.0;
-  d4 buA[RT], buM[RT], buB[RT];
-  P.bu_times(uA, buA);
-
-  const double* recp = a.REC;
-  Rec cur = load_rec<1>(recp);
-  for (int i = 0; i < N; ++i) {
-    // next step's uniform record and control samples are requested now and consumed a step later
-    recp += rec_stride(1);
-    const Rec nxt = load_rec<1>(recp);  // the table is padded past step N-1
-    const int in = i + 1 < N ? i + 1 : i;
-    const Buf bu = Buf::make(a.u + (size_t)(2 * in) * ustride);
-    const double vM = bu.ld(vu, us8), vB = bu.ld(vu, 2 * us8);  // unused control rows read row 0 and are zeroed
-    const double uMn = uact ? vM : 0.0, uBn = uact ? vB : 0.0;
-    P.bu_times(uM, buM);
-    P.bu_times(uB, buB);
-
-    double F1[KS], F2[KS], F3[KS], F4[KS], Y[KS];
-    P.Fx(y, buA, F1);                                                         // :37
-    double cs = P.cost_part(y, uA, cur.tcA[0]);
-#pragma unroll
-    for (int m = 0; m < KS; ++m) Y[m] = __builtin_fma(cur.hh, F1[m], y[m]);   // :40
-    P.Fx(Y, buM, F2);                                                         // :41
-    cs += 2.0 * P.cost_part(Y, uM, cur.tcM[0]);
-#pragma unroll
-    for (int m = 0; m < KS; ++m) Y[m] = __builtin_fma(cur.hh, F2[m], y[m]);   // :44
-    P.Fx(Y, buM, F3);                                                         // :45
-    cs += 2.0 * P.cost_part(Y, uM, cur.tcM[0]);
-#pragma unroll
-    for (int m = 0; m < KS; ++m) Y[m] = __builtin_fma(cur.h, F3[m], y[m]);    // :48
-    P.Fx(Y, buB, F4);                                                         // :49
-    cs += P.cost_part(Y, uB, cur.tcB[0]);
-#pragma unroll
-    for (int m = 0; m < KS; ++m)                                              // :50
-      y[m] = __builtin_fma(cur.h6, (F1[m] + 2.0 * F2[m]) + (2.0 * F3[m] + F4[m]), y[m]);
-    yc = __builtin_fma(cur.h6, sum_over_g(cs), yc);
-    store_x(i + 1);
-    cur = nxt;
-    uA = uB;
-    uM = uMn;
-    uB = uBn;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) buA[rt] = buB[rt];
-  }
-  if (keep && g == 0) a.J[b] = yc;  // J = x(end,end)   :55
-}
 
 // ---------------------------------------------------------------------------------------
 // costate pass   compute_x_lam.m:4,11-14: lam' = -(A' lam + 2 e^{-rt} q .* x), lam(TF) = 0
@@ -230,8 +143,6 @@ __global__ __launch_bounds__(64) void k_lq_sweep_costate(const LQSweepArgs a) {
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-static inline int hip_rc_lqs(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-
 static bool lq_sweep_shape_ok(const ProblemDesc& p, const GridDesc& g, int batch) {
   // (32-bit byte offsets from a buffer base: one column of x is (nS + 1) batch doubles; the state pass reaches three grid
   //  columns of u, 3 nC batch doubles, from the base of the first)
@@ -243,15 +154,11 @@ static bool lq_sweep_shape_ok(const ProblemDesc& p, const GridDesc& g, int batch
 int launch_sweep_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                             double* x, double* J, const int* frozen, const int* gate, hipStream_t s) {
   if (!lq_sweep_shape_ok(p, g, batch) || !x0 || !u || !x || !J) return -1;
-  LQSweepArgs a{};
+  LQArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
-  a.x0 = x0; a.u = u; a.x = x; a.ldx = p.nS + 1; a.J = J; a.frozen = frozen; a.gate = gate;
-  const dim3 grid((batch + 15) / 16), block(64);
-  if (p.nS <= 16)
-    k_lq_sweep_forward<1><<<grid, block, 0, s>>>(a);
-  else
-    k_lq_sweep_forward<2><<<grid, block, 0, s>>>(a);
-  return hip_rc_lqs(hipGetLastError());
+  a.x0 = x0; a.u = u; a.x = x; a.J = J; a.frozen = frozen; a.gate = gate;
+  lq_forward_one_wave(a, s);
+  return hip_rc_lq(hipGetLastError());
 }
 
 int launch_sweep_costate_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx,
@@ -259,13 +166,13 @@ int launch_sweep_costate_lq(const ProblemDesc& p, const GridDesc& g, int batch, 
   if (!lq_sweep_shape_ok(p, g, batch) || !x || !xmid || !lam || ldx != p.nS + 1) return -1;
   LQSweepArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
-  a.x = const_cast<double*>(x); a.ldx = ldx; a.xmid = xmid; a.lam = lam; a.frozen = frozen; a.gate = gate;
+  a.x = x; a.ldx = ldx; a.xmid = xmid; a.lam = lam; a.frozen = frozen; a.gate = gate;
   const dim3 grid((batch + 15) / 16), block(64);
   if (p.nS <= 16)
     k_lq_sweep_costate<1><<<grid, block, 0, s>>>(a);
   else
     k_lq_sweep_costate<2><<<grid, block, 0, s>>>(a);
-  return hip_rc_lqs(hipGetLastError());
+  return hip_rc_lq(hipGetLastError());
 }
 
 }  // namespace ocs

@@ -1,5 +1,5 @@
 """fb_sweep / compute_x_lam(_J) on OCS_PROBLEM_LQ with the state pass and the costate pass on the matrix-core kernels
-(csrc/ocs_lq_sweep_kernels.hip; from eight states on) against the CPU oracle and against the same solve on the problem's
+(csrc/ocs_lq_kernels.hip's one-wave state pass, csrc/ocs_lq_sweep_kernels.hip; from eight states on) against the CPU oracle and against the same solve on the problem's
 plugin form (lane kernels), in the same process.
 
 Inputs: the undamped sweep diverges on lq_matrices(nS, nC) as given once nS >= 8, so the cases weigh the control cost
@@ -203,6 +203,25 @@ def test_compute_x_lam_J(ocs, oracle):
         print(f"compute_x_lam_J instance {b}: x / lam / J {errs}")
         assert max(errs) < 1e-12
         assert np.all(lam[:, N, b] == 0.0)
+
+
+@pytest.mark.parametrize("nS,nC,batch", [(8, 2, 3), (16, 4, 17), (17, 3, 17), (32, 4, 33)])
+def test_state_pass_is_the_integrators_one_wave_pass(ocs, oracle, nS, nC, batch):
+    """The sweep's state pass IS RK4Integrator's one-wave kernel (mapping 1; for nS > 16 the automatic choice is another
+    mapping with another summation order): the state rows of compute_x_lam_J's x and its J equal compute_states' bit for
+    bit.  N = 7 (odd), ragged groups of 16, random u in [-1, 1]."""
+    N = 7
+    pg, _ = make(ocs, oracle, nS, nC)
+    tspan = oracle.linspace(0, 2.0, N + 1)
+    rng = np.random.default_rng(20261019 + nS)
+    u = rng.uniform(-1, 1, (nC, 2 * N + 1, batch))
+    X0 = np.stack([x0_of(nS, (1.0, 4.0, 10.0)[b % 3]) for b in range(batch)], axis=1)
+    integ = ocs.RK4Integrator(tspan)
+    x, _, J = ocs.compute_x_lam_J(pg, X0, tspan, u, integrator=integ)
+    assert ocs.fb_sweep_matrix_core(integ) == 1
+    xi, Ji = ocs.RK4Integrator(tspan).set_mapping(1).compute_states(pg, X0, u)
+    assert np.all(np.isfinite(x)) and np.all(np.isfinite(J))
+    assert np.array_equal(x, xi[:nS]) and np.array_equal(J, Ji)
 
 
 def test_batch_params_are_still_refused(ocs, oracle):
