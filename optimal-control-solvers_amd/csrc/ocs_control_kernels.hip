@@ -13,7 +13,6 @@
 
 namespace ocs {
 
-static inline int hip_rc2(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // u[j][c][b] = sum_{k in col j} v[row[k]][c][b] * val[k]
 __global__ __launch_bounds__(256) void k_basis_expand(int nT, int nC, int batch, const int* __restrict__ colptr,
@@ -159,7 +158,7 @@ int launch_basis_dense(bool expand, int nBasis, int nT, int nC, int batch, const
 #undef OCS_NB
     default: return -1;
   }
-  return hip_rc2(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 // dst[r][b] = src[idx[r]][b]   (gathers rows of a batch-minor array; used for lam(FreeInitStates,1))
@@ -192,31 +191,31 @@ __global__ void k_fill_rows(int ncols, int nC, int batch, const double* __restri
 }
 int launch_add_vec(int n, const double* a, const double* b, double* out, hipStream_t s) {
   k_add_vec<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(n, a, b, out);
-  return hip_rc2(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 int launch_fill_rows(int ncols, int nC, int batch, const double* val, double* out, hipStream_t s) {
   k_fill_rows<<<dim3((batch + 255) / 256, ncols), dim3(256), 0, s>>>(ncols, nC, batch, val, out);
-  return hip_rc2(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 int launch_basis_expand(int nT, int nC, int batch, const int* colptr, const int* row, const double* val,
                         const double* v, double* u, hipStream_t s) {
   k_basis_expand<<<dim3((batch + 255) / 256, nT), dim3(256), 0, s>>>(nT, nC, batch, colptr, row, val, v, u);
-  return hip_rc2(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 int launch_basis_contract(int nBasis, int nC, int batch, const int* rowptr, const int* col, const double* val,
                           const double* dJdu, double* dJdv, hipStream_t s) {
   k_basis_contract<<<dim3((batch + 255) / 256, nBasis), dim3(256), 0, s>>>(nBasis, nC, batch, rowptr, col, val,
                                                                              dJdu, dJdv);
-  return hip_rc2(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 int launch_gather_rows(int nrows, int batch, const int* idx, const double* src, double* dst, hipStream_t s) {
   k_gather_rows<<<dim3((batch + 255) / 256, nrows), dim3(256), 0, s>>>(nrows, batch, idx, src, dst);
-  return hip_rc2(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 int launch_scatter_rows(int nrows, int batch, const int* idx, const double* src, double* dst, hipStream_t s) {
   k_scatter_rows<<<dim3((batch + 255) / 256, nrows), dim3(256), 0, s>>>(nrows, batch, idx, src, dst);
-  return hip_rc2(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

@@ -4,16 +4,9 @@
 
 namespace ocs {
 
-// The wave that carries a kernel's dependent chain (state / costate recursion) may ask the SIMD's arbiter for priority
-// over the helper waves it shares the SIMD with (OCS_CHAIN_PRIO: s_setprio level).  Off: measured with level 3 on the
-// headline pass pair and the folded sweep (scripts/ab_lib.sh) -- state pass 58.9-60.1 -> 60.0-60.7 us, sweep 177.7-178.6
-// -> 179.1-179.4 us: the chain waits for its own results (8 dependent fp64 operations per step), not for issue slots.
-#ifndef OCS_CHAIN_PRIO
-#define OCS_CHAIN_PRIO 0
-#endif
-__device__ static inline void chain_wave_priority() {
-  if (OCS_CHAIN_PRIO) __builtin_amdgcn_s_setprio(OCS_CHAIN_PRIO);
-}
+// The wave that carries a kernel's dependent chain (state / costate recursion) does NOT ask the SIMD's arbiter for priority
+// over the helper waves it shares the SIMD with: s_setprio 3 on it measured slower (NOTES.md, "Tuning switches taken out") --
+// the chain waits for its own results (8 dependent fp64 operations per step), not for issue slots.
 
 #define OCS_INLINE __attribute__((always_inline))
 
@@ -23,9 +16,6 @@ __device__ static inline void chain_wave_priority() {
 // instance twice, they are only compared with zero).  Launchers ask for it with batch > TPW and an even batch (16-byte DMA chunks).
 __device__ static inline int tile_base(int block, int TPW, int batch) {
   const int b0 = block * TPW;
-#ifdef OCS_NO_TILE_OVERLAP   // (A/B builds)
-  return b0;
-#endif
   return b0 + TPW <= batch ? b0 : batch - TPW;
 }
 

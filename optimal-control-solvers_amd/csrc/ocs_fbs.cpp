@@ -628,8 +628,8 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   // ... and the same for error points OFF the grid nodes (the reference's default of 1001 points on any grid but N = 1000, a given
   // u0): the kernels of the kernel-by-kernel sequence below, gated and enqueued ahead (path 5).  That sequence waited for the
   // host once per sweep: 485 against ~250 us per sweep at 500 steps.
-  const bool ahead1 = !fusedup && fuo == 0 && forward_gate_any(pd);
-  if ((fusedup && (fold || forward_gate_any(pd))) || ahead1) {
+  const bool ahead1 = !fusedup && fuo == 0;
+  if (fusedup || ahead1) {
     const int nsw = opt->nSWEEPS;
     const bool ownx = !lqmc && fuo == 0 && costate_forms_midpoints(pd, N, batch);   // midpoints inside the costate / control kernels
     f->last_path = fold ? 4 : (fusedup ? 2 : 5);
@@ -671,40 +671,37 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
                                      opt->cost_row == 0, gate, sweep == 1, s));
         LAUNCH_TRY(launch_costate_met(pd, gd, batch, xaug, nAug, tb.PR, p->d_lb.d(), p->d_ub.d(), opt->uRelTol,
                                       opt->uAbsTol, sweep, status, mc, dslots + (sweep - 1), lam, s, gate));
-        HIP_TRY(hipMemcpyAsync(f->h_nact + (sweep - 1), dslots + (sweep - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(f->wevents[sweep % nev], s));
-        return OCS_OK;
+      } else {
+        FwdOpts fo;
+        fo.frozen = status;
+        fo.dump = f->dump.d();
+        fo.no_cost_row = opt->cost_row == 0;
+        fo.gate = gate;
+        LAUNCH_TRY(state_pass(fo));
+        const double* xmid = ownx ? nullptr : f->xmid.d();
+        if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s, gate));
+        LAUNCH_TRY(costate_pass(xmid, tb.PR, gate));
+        if (!fusedup) {   // error points off the nodes: uNew there with check_convergence (:96, :99-115), then u = uNew on the grid
+          if (cps)
+            LAUNCH_TRY(launch_control_pts_sorted(pd, tb, nE, (const int*)f->QSE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
+                                                 f->uerr.d(), f->metric.d(), opt->uRelTol, opt->uAbsTol, s, om, gate));
+          else
+            LAUNCH_TRY(launch_control_pts(pd, tb, nE, (const int*)f->KE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
+                                          f->uerr.d(), usel, (long long)uerrN, f->metric.d(), (int*)f->anyvalid.p, opt->uRelTol,
+                                          opt->uAbsTol, s, om, gate));
+          LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
+                                        mc, dslots + (sweep - 1), s, gate));
+          // (only the instances that continue take uNew: status is the one k_fbs_advance just wrote, :85 / :82)
+          LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, nullptr, 0.0, 0.0, s, gate,
+                                         om));
+        } else {
+          LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, f->metric.d(),
+                                         opt->uRelTol, opt->uAbsTol, s, gate, om));
+          LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
+                                        mc, dslots + (sweep - 1), s, gate));
+        }
       }
-      FwdOpts fo;
-      fo.frozen = status;
-      fo.dump = f->dump.d();
-      fo.no_cost_row = opt->cost_row == 0;
-      fo.gate = gate;
-      LAUNCH_TRY(state_pass(fo));
-      const double* xmid = ownx ? nullptr : f->xmid.d();
-      if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s, gate));
-      LAUNCH_TRY(costate_pass(xmid, tb.PR, gate));
-      if (!fusedup) {   // error points off the nodes: uNew there with check_convergence (:96, :99-115), then u = uNew on the grid
-        if (cps)
-          LAUNCH_TRY(launch_control_pts_sorted(pd, tb, nE, (const int*)f->QSE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
-                                               f->uerr.d(), f->metric.d(), opt->uRelTol, opt->uAbsTol, s, om, gate));
-        else
-          LAUNCH_TRY(launch_control_pts(pd, tb, nE, (const int*)f->KE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
-                                        f->uerr.d(), usel, (long long)uerrN, f->metric.d(), (int*)f->anyvalid.p, opt->uRelTol,
-                                        opt->uAbsTol, s, om, gate));
-        LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
-                                      mc, dslots + (sweep - 1), s, gate));
-        // (only the instances that continue take uNew: status is the one k_fbs_advance just wrote, :85 / :82)
-        LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, nullptr, 0.0, 0.0, s, gate,
-                                       om));
-        HIP_TRY(hipMemcpyAsync(f->h_nact + (sweep - 1), dslots + (sweep - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(f->wevents[sweep % nev], s));
-        return OCS_OK;
-      }
-      LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, f->metric.d(),
-                                     opt->uRelTol, opt->uAbsTol, s, gate, om));
-      LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
-                                    mc, dslots + (sweep - 1), s, gate));
+      // the sweep's count of active instances to the host, and the event the host waits on
       HIP_TRY(hipMemcpyAsync(f->h_nact + (sweep - 1), dslots + (sweep - 1), sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipEventRecord(f->wevents[sweep % nev], s));
       return OCS_OK;

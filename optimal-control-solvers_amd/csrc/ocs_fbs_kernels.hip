@@ -18,19 +18,10 @@
 
 namespace ocs {
 
-static inline int hip_rc3(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-#define OCS_DISPATCH_LOGISTIC2(NSV, CALL) \
-  switch (NSV) {                          \
-    case 1: { using P = LogisticK<1>; CALL; } break; \
-    case 2: { using P = LogisticK<2>; CALL; } break; \
-    case 3: { using P = LogisticK<3>; CALL; } break; \
-    case 4: { using P = LogisticK<4>; CALL; } break; \
-    default: return -1;                   \
-  }
 
 static PchipTab make_tab(const FbsTables& t) { return PchipTab{t.n, t.TN, t.HN, t.W1, t.W2, t.IH}; }
 
@@ -38,7 +29,7 @@ int launch_pchip_mid(const FbsTables& t, int nrows, int ld, int batch, const dou
                      const int* gate) {
   k_pchip_mid<<<dim3((batch + 255) / 256, (t.n - 1 + kPchipRun - 1) / kPchipRun), dim3(256), 0, s>>>(
       make_tab(t), nrows, ld, batch, t.TM, V, out, gate);
-  return hip_rc3(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 // whether launch_costate takes xmid == NULL (with PR) and forms the pchip midpoints of x itself
@@ -82,8 +73,8 @@ int launch_costate(const ProblemDesc& p, const GridDesc& g, int batch, const dou
     return jit_launch(p.user, UK_COSTATE, dim3((batch + 63) / 64), dim3(64), args, s);
   }
   if (p.functor != Functor::Logistic) return -1;
-  OCS_DISPATCH_LOGISTIC2(p.nS, run_costate<P>(a, s));
-  return hip_rc3(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_costate<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 template <class P>
@@ -102,8 +93,8 @@ int launch_control_grid(const ProblemDesc& p, const GridDesc& g, const FbsTables
     return jit_launch(p.user, UK_CONTROL_GRID, dim3((batch + 255) / 256, (g.N + kPchipRun - 1) / kPchipRun), dim3(256), args, s);
   }
   if (p.functor != Functor::Logistic) return -1;
-  OCS_DISPATCH_LOGISTIC2(p.nS, run_control_grid<P>(a, s));
-  return hip_rc3(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_control_grid<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 template <class P>
@@ -123,8 +114,8 @@ int launch_control_pts(const ProblemDesc& p, const FbsTables& t, int nq, const i
                       dim3(256), args, s);
   }
   if (p.functor != Functor::Logistic) return -1;
-  OCS_DISPATCH_LOGISTIC2(p.nS, run_control_pts<P>(a, s));
-  return hip_rc3(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_control_pts<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 template <class P>
@@ -138,22 +129,22 @@ int launch_tu_at(const ProblemDesc& p, int nq, const double* tq, double* TUQ, hi
     return jit_launch(p.user, UK_TU_AT, dim3((nq + 255) / 256), dim3(256), args, s);
   }
   if (p.functor != Functor::Logistic) return -1;
-  OCS_DISPATCH_LOGISTIC2(p.nS, run_tu_at<P>(nq, tq, p.ps, TUQ, s));
-  return hip_rc3(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_tu_at<decltype(P)>(nq, tq, p.ps, TUQ, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 int launch_interp(int method, const FbsTables& t, int nComp, int nq, const int* KQ, const double* SQ, int batch,
                   const double* V, double* out, hipStream_t s) {
   k_interp<<<dim3((batch + 255) / 256, (nq + kInterpPts - 1) / kInterpPts, nComp), dim3(256), 0, s>>>(
       method, make_tab(t), nComp, nq, batch, KQ, SQ, V, out);
-  return hip_rc3(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 int launch_interp_pchip_sorted(const FbsTables& t, int nComp, const int* QS, const int* QI, const double* SS, int batch,
                                const double* V, double* out, hipStream_t s) {
   k_interp_pchip_sorted<<<dim3((batch + 255) / 256, (t.n - 1 + kInterpRun - 1) / kInterpRun, nComp), dim3(256), 0, s>>>(
       make_tab(t), nComp, batch, QS, QI, SS, V, out);
-  return hip_rc3(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 // start of a solve: usel = 0, status = 0, maxChange = NaN (all-ones) in one launch instead of three memsets
@@ -169,7 +160,7 @@ __global__ void k_fbs_init(int batch, long long nmc, int* __restrict__ usel, int
 int launch_fbs_init(int batch, int nsweeps, int* usel, int* status, double* maxChange, hipStream_t s) {
   const long long nmc = (long long)nsweeps * batch;
   k_fbs_init<<<dim3((unsigned)((nmc + 255) / 256)), dim3(256), 0, s>>>(batch, nmc, usel, status, (unsigned long long*)maxChange);
-  return hip_rc3(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 int control_pts_parts(int nq) { return (nq + kPtsPerThread - 1) / kPtsPerThread; }
@@ -193,14 +184,14 @@ int launch_control_pts_sorted(const ProblemDesc& p, const FbsTables& t, int nq, 
     void* args[] = {(void*)&a, (void*)&QS};
     return jit_launch(p.user, UK_CONTROL_PTS_SORTED, dim3((batch + 255) / 256, (t.n - 1 + kCtlRun - 1) / kCtlRun), dim3(256), args, s);
   }
-  OCS_DISPATCH_LOGISTIC2(p.nS, run_control_pts_sorted<P>(a, QS, s));
-  return hip_rc3(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_control_pts_sorted<decltype(P)>(a, QS, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 int launch_fbs_advance(int batch, int sweep, int nparts, const double* metric, int* anyvalid, int* usel, int* status,
                        double* maxChange, int* nactive, hipStream_t s, const int* gate) {
   k_fbs_advance<<<dim3((batch + 63) / 64), dim3(64), 0, s>>>(batch, sweep, nparts, metric, anyvalid, usel, status,
                                                                  maxChange, nactive, gate);
-  return hip_rc3(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

@@ -30,12 +30,9 @@
 
 namespace ocs {
 
-#ifndef OCS_FOLD_G1_LDS
-#define OCS_FOLD_G1_LDS 0   // tuning builds: 1 = one-row problems take the interval records through LDS as well
-#endif
 template <int G>
 struct FoldCfg {
-  static constexpr bool PRL = G > 1 || OCS_FOLD_G1_LDS;      // interval records and ControlChar coefficients through LDS
+  static constexpr bool PRL = G > 1;   // interval records and ControlChar coefficients through LDS (one-row problems too: not faster, NOTES.md)
   static constexpr int D = 8, TPW = 64 / G;
   static constexpr int Q = 5;
   static constexpr int NSLOT = Q + 7;
@@ -59,14 +56,8 @@ struct FoldCfg {
   static_assert(REC_DBL == 128 && (!PRL || PR_DBL == 128) && Q * LPB <= 63, "block shapes");
   // wave -> role: the recursion wave shares its SIMD (waves w, w+4, w+8, w+12) with the light roles only
   enum Role { M_ = 0, S_ = 1, P_ = 2, J_ = 3, C_ = 4, U_ = 5 };
-#ifndef OCS_FOLD_ROLEMAP
-#define OCS_FOLD_ROLEMAP 0   // tuning builds: 1 = a control wave on the recursion wave's SIMD in the place of M, 2 = two (M and J out)
-#endif
+  // (control waves on the recursion wave's SIMD in the place of M, or of M and J: within 1 % or slower, NOTES.md)
   __device__ static constexpr int role(int w) {
-    if (G == 1 && OCS_FOLD_ROLEMAP == 1)
-      return w == 1 ? S_ : w == 5 ? P_ : w == 9 ? J_ : w == 14 ? M_ : (w == 0 || (w >= 2 && w <= 4)) ? C_ : U_;
-    if (G == 1 && OCS_FOLD_ROLEMAP == 2)
-      return w == 1 ? S_ : w == 5 ? P_ : w == 10 ? J_ : w == 14 ? M_ : (w == 0 || (w >= 2 && w <= 4)) ? C_ : U_;
     return G == 1 ? (w == 1 ? S_ : w == 5 ? P_ : w == 9 ? J_ : w == 13 ? M_ : (w == 0 || (w >= 2 && w <= 4)) ? C_ : U_)
          : G == 2 ? (w == 0 ? M_ : w == 1 ? S_ : w == 5 ? P_ : w == 9 ? J_ : (w == 2 || w == 3 || w == 4 || w == 6) ? C_ : U_)
                   : (w == 0 ? M_ : w == 1 ? S_ : w == 5 ? P_ : w == 4 ? J_ : (w == 2 || w == 3) ? C_ : U_);
@@ -265,7 +256,6 @@ __global__ __launch_bounds__(FoldCfg<P::NS>::NWAVE * 64) void k_forward_cc(const
     P2_END(wave);
   } else if (role == C_::S_) {
     // ---------------- S: the recursion (k_forward_p2's) ----------------
-    chain_wave_priority();
     const int r = lane / TPW, tl = lane % TPW, b = bw + tl;
     const typename P::RowPar rp = P::load_row(ParamSrc{PS, a.pb, a.pmask, B, b}, r);
     const bool fz = a.frozen != nullptr && a.frozen[b] != 0;
@@ -288,15 +278,7 @@ __global__ __launch_bounds__(FoldCfg<P::NS>::NWAVE * 64) void k_forward_cc(const
         auto fetch = [&](int s) OCS_INLINE {
           In v;
           v.c = pw[s * 64];
-#ifndef OCS_FOLD_SREC
-#define OCS_FOLD_SREC 0   // tuning builds: 1 = the recursion wave takes the step sizes with scalar loads from the record table
-#endif
-          if (!UNI && OCS_FOLD_SREC) {
-            const uniform_ptr rq = R0 + (size_t)(k * D + s) * RS;
-            v.h = rq[0];
-            v.hh = rq[1];
-            v.h6 = rq[2];
-          } else if (!UNI) {
+          if (!UNI) {   // from the block's slot in LDS (scalar loads from the record table: slower, NOTES.md)
             v.h = rec[RS * s];
             v.hh = rec[RS * s + 1];
             v.h6 = rec[RS * s + 2];
@@ -305,22 +287,12 @@ __global__ __launch_bounds__(FoldCfg<P::NS>::NWAVE * 64) void k_forward_cc(const
           }
           return v;
         };
-#ifndef OCS_FOLD_SPF
-#define OCS_FOLD_SPF 1   // steps the recursion wave reads its inputs ahead of their use (tuning builds: 2)
-#endif
-        In nxt = fetch(0);
-        In nx2 = nxt;
-        if (OCS_FOLD_SPF == 2) nx2 = fetch(1);
+        In nxt = fetch(0);   // the recursion wave reads its inputs one step ahead of their use (two: no gain, NOTES.md)
         if constexpr (P::HAS_SHIFT) {
 #pragma unroll
           for (int s = 0; s < D; ++s) {
             const In c = nxt;
-            if (OCS_FOLD_SPF == 2) {
-              nxt = nx2;
-              if (s + 2 < D) nx2 = fetch(s + 2);
-            } else if (s + 1 < D) {
-              nxt = fetch(s + 1);
-            }
+            if (s + 1 < D) nxt = fetch(s + 1);
             __builtin_amdgcn_sched_barrier(0);
             const double cM = c.c.x, cB = c.c.y;
             zw[s * 64] = z;

@@ -8,7 +8,6 @@
 
 namespace ocs {
 
-static inline int hip_rc7(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 bool fold_supported(const ProblemDesc& p, const GridDesc& g, int batch) {
   if (p.nC != 1 || !(p.nS == 1 || p.nS == 2 || p.nS == 4)) return false;
@@ -38,12 +37,7 @@ int launch_forward_cc(const ProblemDesc& p, const GridDesc& g, int batch, const 
     void* args[] = {(void*)&a};
     return jit_launch(p.user, g.uniform ? UK_FWD_CC_UNI : UK_FWD_CC, dim3(tile_count(batch, 64 / p.nS)), dim3(nwave * 64), args, s);
   }
-  if (p.nS == 1)
-    run_forward_cc<LogisticK<1>>(a, g.uniform, s);
-  else if (p.nS == 2)
-    run_forward_cc<LogisticK<2>>(a, g.uniform, s);
-  else
-    run_forward_cc<LogisticK<4>>(a, g.uniform, s);
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_forward_cc<decltype(P)>(a, g.uniform, s); })) return -1;
 #ifdef OCS_P2_STAMPS
   {
     static int calls = 0;
@@ -60,7 +54,7 @@ int launch_forward_cc(const ProblemDesc& p, const GridDesc& g, int batch, const 
     }
   }
 #endif
-  return hip_rc7(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

@@ -19,7 +19,6 @@
 
 namespace ocs {
 
-static inline int hip_rc_fb(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // column table entry: {w0, w1, adv, pad}; adv = r_j - r_{j-1} (0 or 1; r_0 in the header of the args)
 constexpr int kBandRec = 4;
@@ -360,14 +359,8 @@ static void run_fb(bool forward, const FbArgs& a, hipStream_t s) {
 }
 static int launch_fb(bool forward, const ProblemDesc& p, const FbArgs& a, hipStream_t s) {
   if (!fused_banded_supported(p.functor, p.nS, p.nC) || a.N < 1) return -1;
-  switch (p.nS) {
-    case 1: run_fb<LogisticK<1>>(forward, a, s); break;
-    case 2: run_fb<LogisticK<2>>(forward, a, s); break;
-    case 3: run_fb<LogisticK<3>>(forward, a, s); break;
-    case 4: run_fb<LogisticK<4>>(forward, a, s); break;
-    default: return -1;
-  }
-  return hip_rc_fb(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_fb<decltype(P)>(forward, a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 int launch_forward_fb(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, int r0, const double* CT,
                       const double* v, const double* x0, double* ck, double* J, hipStream_t s) {

@@ -30,7 +30,6 @@
 
 namespace ocs {
 
-static inline int hip_rc_fc(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // One group of 16 basis functions.  Each product is `v_fmac_f64_dpp acc, brow, x row_newbcast:k`:
 // acc += (lane k of the own 16-lane row of brow) * x = B(k,j) * x.  All 16 sit in ONE asm statement that starts
@@ -841,14 +840,8 @@ static void run_fc(bool forward, const FcArgs& a, hipStream_t s) {
 static int launch_fc(bool forward, const ProblemDesc& p, const FcArgs& a, hipStream_t s) {
   if (!fused_control_supported(p.functor, p.nS, p.nC, a.nBasis)) return -1;
   const bool two = a.nBasis > 16;
-  switch (p.nS) {
-    case 1: two ? run_fc<LogisticK<1>, 2>(forward, a, s) : run_fc<LogisticK<1>, 1>(forward, a, s); break;
-    case 2: two ? run_fc<LogisticK<2>, 2>(forward, a, s) : run_fc<LogisticK<2>, 1>(forward, a, s); break;
-    case 3: two ? run_fc<LogisticK<3>, 2>(forward, a, s) : run_fc<LogisticK<3>, 1>(forward, a, s); break;
-    case 4: two ? run_fc<LogisticK<4>, 2>(forward, a, s) : run_fc<LogisticK<4>, 1>(forward, a, s); break;
-    default: return -1;
-  }
-  return hip_rc_fc(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { two ? run_fc<decltype(P), 2>(forward, a, s) : run_fc<decltype(P), 1>(forward, a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 // BT16: transposed basis [2N+1][16 or 32] zero-padded (16 when nBasis <= 16)
 int launch_forward_fc(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, const double* BT16,

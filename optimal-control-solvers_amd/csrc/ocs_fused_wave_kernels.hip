@@ -35,7 +35,6 @@
 
 namespace ocs {
 
-static inline int hip_rc_fw(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 typedef double d4_fw __attribute__((ext_vector_type(4)));
 __device__ static inline d4_fw mma_fw(double a, double b, d4_fw c) {
@@ -439,7 +438,7 @@ int launch_forward_fcw(const ProblemDesc& p, const GridDesc& g, int batch, int n
     }
   }
 #endif
-  return hip_rc_fw(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 int launch_backward_fcs(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, int ldbt, const double* BT,
                         const double* v, const double* ck, double* dJdv, double* lam0, hipStream_t s) {
@@ -467,7 +466,7 @@ int launch_backward_fcs(const ProblemDesc& p, const GridDesc& g, int batch, int 
     }
   }
 #endif
-  return hip_rc_fw(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

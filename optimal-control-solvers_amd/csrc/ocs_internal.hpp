@@ -7,6 +7,9 @@
 
 namespace ocs {
 
+// what a launcher returns: 0, or the HIP error as it is
+inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
+
 // Which device functor a problem handle resolves to.
 enum class Functor : int { Logistic = 1, LQ = 3, User = 100 };
 struct UserModule;  // hipRTC-compiled user problem (ocs_jit.hpp)
@@ -123,8 +126,6 @@ bool forward_gate_supported(const ProblemDesc& p, const GridDesc& g, int batch);
 // workgroups (of 64/nS trajectories) up to which fb_sweep takes its wave-specialised kernels (the folded two-kernel sweep, the
 // costate kernels that form the midpoints of x); OCS_FOLD_MAX_WG overrides (tuning)
 int fold_wg_limit();
-// ... any state pass the sweep launches (with FwdOpts::frozen set) honours the gate, LQ excepted
-bool forward_gate_any(const ProblemDesc& p);
 bool rowsplit_supported(Functor f, int nS, int nC);
 int launch_forward_rs(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                       double* x, double* J, hipStream_t s);

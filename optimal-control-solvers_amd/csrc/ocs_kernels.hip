@@ -22,7 +22,6 @@
 
 namespace ocs {
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // ---------------------------------------------------------------------------------------
 // layout helpers: 64x64 LDS-tiled transposes between [batch][per] and [per][batch]
@@ -64,14 +63,6 @@ __global__ void k_count_nonfinite(const double* __restrict__ v, int n, int* __re
 // ---------------------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------------------
-#define OCS_DISPATCH_LOGISTIC(NSV, CALL) \
-  switch (NSV) {                         \
-    case 1: { using P = LogisticK<1>; CALL; } break; \
-    case 2: { using P = LogisticK<2>; CALL; } break; \
-    case 3: { using P = LogisticK<3>; CALL; } break; \
-    case 4: { using P = LogisticK<4>; CALL; } break; \
-    default: return -1;                  \
-  }
 
 bool functor_supported(Functor f, int nS, int nC) {
   if (f == Functor::User) return true;
@@ -118,7 +109,7 @@ int launch_tcoef(const ProblemDesc& p, const GridDesc& g, hipStream_t s) {
     return jit_launch(p.user, UK_BUILD_REC, dim3((N + 2 * kRecPad + 255) / 256), dim3(256), a2, s);
   }
   if (p.functor == Functor::LQ) return launch_tcoef_lq(p, g, s);
-  OCS_DISPATCH_LOGISTIC(p.nS, run_tcoef<P>(p, g, s));
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_tcoef<decltype(P)>(p, g, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
 int rec_stride_host(int ntc) { return rec_stride(ntc); }
@@ -221,12 +212,11 @@ bool tail_leg_wave_ok(const ProblemDesc& p, const GridDesc& g, int batch) {
   if (p.functor == Functor::LQ) return false;
   return choose_mapping(p, g.N, batch, MAP_AUTO, true, false, true) == MAP_PIPELINE;
 }
-// any state pass the sweep launches with `frozen` set (pipeline kernels, split passes, the lane kernel): FwdOpts::gate
-bool forward_gate_any(const ProblemDesc& p) { return p.functor != Functor::LQ; }
-
+// FwdOpts::gate: honoured by any state pass the sweep launches with `frozen` set (pipeline kernels, split passes, the lane
+// kernel), refused on the LQ functor (the sweep runs that problem's plugin twin or its own matrix-core passes)
 int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                    double* x, double* J, const FwdOpts& o, hipStream_t s) {
-  if (o.gate && (o.mapping != MAP_AUTO || o.uconst || o.Jadd || !forward_gate_any(p) || !o.frozen)) return -1;
+  if (o.gate && (o.mapping != MAP_AUTO || o.uconst || o.Jadd || p.functor == Functor::LQ || !o.frozen)) return -1;
   if (p.functor == Functor::LQ) return launch_forward_lq(p, g, batch, x0, u, x, J, o, s);
   const bool plain = !o.uconst && !o.Jadd;
   // (MAP_SCAN names the adjoint kernel; the state pass of such an integrator is chosen automatically)
@@ -256,7 +246,7 @@ int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const dou
       void* args[] = {(void*)&a};
       return jit_launch(p.user, UK_FWD_X, dim3((batch + 63) / 64), dim3(64), args, s);
     }
-    OCS_DISPATCH_LOGISTIC(p.nS, run_forward<P>(a, false, s));
+    if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_forward<decltype(P)>(a, false, s); })) return -1;
     return hip_rc(hipGetLastError());
   }
   if (map == MAP_ROWSPLIT) {
@@ -271,7 +261,7 @@ int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const dou
     const int kid = o.uconst ? UK_FWD_UCONST : (x ? UK_FWD_X : UK_FWD_J);
     return jit_launch(p.user, kid, dim3((batch + 63) / 64), dim3(64), args, s);
   }
-  OCS_DISPATCH_LOGISTIC(p.nS, run_forward<P>(a, o.uconst, s));
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_forward<decltype(P)>(a, o.uconst, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
 
@@ -321,14 +311,15 @@ int launch_backward(const ProblemDesc& p, const GridDesc& g, int batch, const do
     return vscan ? launch_backward_vscan(p, gg, batch, xck, u, lT, lam, dJdu, o.lam0, pend0, s)
                  : launch_backward_scan(p, gg, batch, xck, u, lT, lam, dJdu, o.lam0, pend0, s);
   };
-  if (map == MAP_SCAN) {
-    if (!scan_ok && !vscan) return -1;
-    if (Ns == g.N) return scan_launch(g, lamT, nullptr);
+  // A split pass: steps N-1 .. N1 first, on the lane kernel -- lam columns N1..N, dJdu columns 2 N1 .. 2 N (column 2 N1 holds
+  // the k1 half only, RK4Integrator.m:108-112) -- then whole(g1, lamb, db): the whole blocks or chunks below, started from
+  // lam(:, N1) and adding their k4 half to column 2 N1.
+  auto split_at = [&](int N1, auto&& whole) -> int {
     const size_t col = (size_t)(p.nS + 1) * batch, ucol = (size_t)p.nC * batch;
-    double* lamb = lam ? lam + (size_t)Ns * col : o.split_scratch;   // lam(:, Ns): in the output array, or as lam0
-    double* db = dJdu ? dJdu + (size_t)(2 * Ns) * ucol : nullptr;
-    const BwdArgs a{g.N - Ns, batch, g.REC + (size_t)Ns * rec_stride_host(functor_ntc(p.functor, p.nS)), p.ps, p.pb,
-                    p.pmask, xck + (size_t)Ns * col, u + (size_t)(2 * Ns) * ucol, lamT, lam ? lamb : nullptr, db,
+    double* lamb = lam ? lam + (size_t)N1 * col : o.split_scratch;   // lam(:, N1): in the output array, or as lam0
+    double* db = dJdu ? dJdu + (size_t)(2 * N1) * ucol : nullptr;
+    const BwdArgs a{g.N - N1, batch, g.REC + (size_t)N1 * rec_stride_host(functor_ntc(p.functor, p.nS)), p.ps, p.pb,
+                    p.pmask, xck + (size_t)N1 * col, u + (size_t)(2 * N1) * ucol, lamT, lam ? lamb : nullptr, db,
                     lam ? nullptr : lamb};
     int rc;
     if (p.functor == Functor::User) {
@@ -336,32 +327,26 @@ int launch_backward(const ProblemDesc& p, const GridDesc& g, int batch, const do
       rc = jit_launch(p.user, a.lam && a.dJdu ? UK_BWD_LAM_DJDU : (a.lam ? UK_BWD_LAM : UK_BWD_DJDU),
                       dim3((batch + 63) / 64), dim3(64), args, s);
     } else {
-      OCS_DISPATCH_LOGISTIC(p.nS, run_backward<P>(a, false, s));
+      if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_backward<decltype(P)>(a, false, s); })) return -1;
       rc = hip_rc(hipGetLastError());
     }
     if (rc) return rc;
     GridDesc g1 = g;
-    g1.N = Ns;
-    return scan_launch(g1, lamb, db);
+    g1.N = N1;
+    return whole(g1, lamb, db);
+  };
+  if (map == MAP_SCAN) {
+    if (!scan_ok && !vscan) return -1;
+    if (Ns == g.N) return scan_launch(g, lamT, nullptr);
+    return split_at(Ns, scan_launch);
   }
   if (map == MAP_PIPELINE) {
     const int N1 = plain ? pipeline_steps(p, g.N, batch, true) : 0;
     if (N1 == 0 || (N1 < g.N && !lam)) return -1;  // the split hands lam(:, N1) over through memory
     if (N1 == g.N) return launch_backward_pl(p, g, batch, xck, u, lamT, lam, dJdu, o.lam0, nullptr, s);
-    // steps N-1 .. N1 first, on the lane kernel: lam columns N1..N, dJdu columns 2 N1 .. 2 N (column 2 N1 holds the
-    // k1 half only, RK4Integrator.m:108-112) ...
-    const size_t col = (size_t)(p.nS + 1) * batch, ucol = (size_t)p.nC * batch;
-    double* lamb = lam + (size_t)N1 * col;
-    double* db = dJdu ? dJdu + (size_t)(2 * N1) * ucol : nullptr;
-    const BwdArgs a{g.N - N1, batch, g.REC + (size_t)N1 * rec_stride_host(functor_ntc(p.functor, p.nS)), p.ps, p.pb,
-                    p.pmask, xck + (size_t)N1 * col, u + (size_t)(2 * N1) * ucol, lamT, lamb, db, nullptr};
-    OCS_DISPATCH_LOGISTIC(p.nS, run_backward<P>(a, false, s));
-    int rc = hip_rc(hipGetLastError());
-    if (rc) return rc;
-    // ... then the whole blocks below, started from lam(:, N1) and adding their k4 half to column 2 N1
-    GridDesc g1 = g;
-    g1.N = N1;
-    return launch_backward_pl(p, g1, batch, xck, u, lamb, lam, dJdu, o.lam0, db, s);
+    return split_at(N1, [&](const GridDesc& g1, const double* lamb, const double* db) {
+      return launch_backward_pl(p, g1, batch, xck, u, lamb, lam, dJdu, o.lam0, db, s);
+    });
   }
   if (map == MAP_ROWSPLIT) {
     if (!plain || !rowsplit_supported(p.functor, p.nS, p.nC)) return -1;
@@ -376,7 +361,7 @@ int launch_backward(const ProblemDesc& p, const GridDesc& g, int batch, const do
     if (kid == UK_BWD_LAM_DJDU && xmin > 0 && batch >= xmin && g.N >= 4 && p.nS <= 4) kid = UK_BWD_LAM_DJDU_XRC;
     return jit_launch(p.user, kid, dim3((batch + 63) / 64), dim3(64), args, s);
   }
-  OCS_DISPATCH_LOGISTIC(p.nS, run_backward<P>(a, o.uconst, s));
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_backward<decltype(P)>(a, o.uconst, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
 
@@ -393,7 +378,7 @@ int launch_eval(const ProblemDesc& p, int which, int k, const double* t, const d
     return jit_launch(p.user, UK_EVAL, dim3((k + 127) / 128), dim3(128), args, s);
   }
   if (p.functor == Functor::LQ) return which == 3 ? -1 : launch_eval_lq(p, which, k, t, y, u, v, out, s);   // (ControlChar: its plugin twin)
-  OCS_DISPATCH_LOGISTIC(p.nS, run_eval<P>(p, which, k, t, y, u, v, out, s));
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_eval<decltype(P)>(p, which, k, t, y, u, v, out, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
 
@@ -410,7 +395,7 @@ int launch_equilibrium(const ProblemDesc& p, int batch, double r, const double* 
     return jit_launch(p.user, UK_EQUILIBRIUM, dim3((batch + 63) / 64), dim3(64), args, s);
   }
   if (p.functor != Functor::Logistic) return -1;
-  OCS_DISPATCH_LOGISTIC(p.nS, run_equilibrium<P>(a, s));
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_equilibrium<decltype(P)>(a, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
 

@@ -10,8 +10,6 @@ namespace ocs {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-static inline int hip_rc_lq(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-
 // time coefficients of the LQ problem for the shared table builders (k_tcoef / k_build_rec)
 struct LQTime {
   static constexpr int NTC = 1, NTU = 1, NSC = 0;

@@ -32,7 +32,7 @@ int launch_tcoef_lq(const ProblemDesc& p, const GridDesc& g, hipStream_t s) {
   const int nT = 2 * g.N + 1;
   k_tcoef<LQTime><<<dim3((nT + 255) / 256), dim3(256), 0, s>>>(nT, g.T, p.ps, g.TC, g.TU);
   k_build_rec<LQTime><<<dim3((g.N + 2 * kRecPad + 255) / 256), dim3(256), 0, s>>>(g.N, g.HT, g.TC, g.REC);
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1623,7 +1623,7 @@ static int lq_chunk_matrices(LqWorkspace* w, const ProblemDesc& p, const GridDes
   k_lq_forward<RT, false, true, 1><<<dim3(nU / 16, C), dim3(64), 0, s>>>(a);
   w->key_ps = p.ps; w->key_version = p.version; w->key_rec = g.REC; w->key_C = C; w->key_N = g.N; w->key_nS = nS;
   w->zc_valid = false;
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 template <int RT, bool PW>
@@ -1672,7 +1672,7 @@ static int lq_forward_chunked(const ProblemDesc& p, const GridDesc& g, int batch
   else k_lq_forward<RT, false, false, 2, PW><<<grid, block, 0, s>>>(a);
   k_lq_cost_prefix<<<dim3((batch + 255) / 256), dim3(256), 0, s>>>(batch, C, w->cj, w->off, o.Jadd, J);
   if (x && N > L) k_lq_cost_fix<<<dim3((batch + 255) / 256, N - L), dim3(256), 0, s>>>(batch, nS, N, L, w->off, x);
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 template <int RT, bool PW>
@@ -1703,14 +1703,14 @@ static int lq_backward_chunked(const ProblemDesc& p, const GridDesc& g, int batc
   k_lq_carry<true><<<dim3((batch + 63) / 64), dim3(256), 0, s>>>(nS, nU, batch, C, w->MT, lamT, w->ce, w->cs, last, batch);
   if (o.uconst) {   // the constant objective row of lam(:,1)
     k_lq_set_row<<<dim3((batch + 255) / 256), dim3(256), 0, s>>>(batch, o.lam0 + (size_t)nS * B, lamT ? lamT + (size_t)nS * B : nullptr);
-    return hip_rc_lq(hipGetLastError());
+    return hip_rc(hipGetLastError());
   }
   a.ce = nullptr; a.cs = w->cs; a.cj = w->cj; a.lam = lam; a.dJdu = dJdu; a.lam0 = o.lam0;
   if (lam && dJdu) k_lq_backward<RT, true, true, false, 2, PW><<<grid, block, 0, s>>>(a);
   else if (lam) k_lq_backward<RT, true, false, false, 2, PW><<<grid, block, 0, s>>>(a);
   else k_lq_backward<RT, false, true, false, 2, PW><<<grid, block, 0, s>>>(a);
   if (dJdu && C > 1) k_lq_djdu_fix<<<dim3((batch + 255) / 256, C - 1, nC), dim3(256), 0, s>>>(batch, nC, L, C, w->cj, dJdu);
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1798,7 +1798,7 @@ static int lq_forward_dispatch(const ProblemDesc& p, const GridDesc& g, int batc
     case LqMap::TwoWaves: run_lq_forward<LqM2, PW>(a, o.uconst, s); break;
     case LqMap::FourWaves: run_lq_forward<LqM4, PW>(a, o.uconst, s); break;
   }
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 // fb_sweep's state pass (launch_sweep_forward_lq): the one-wave pass with every output, SWEEP
 void lq_forward_one_wave(const LQArgs& a, hipStream_t s) {
@@ -1845,7 +1845,7 @@ static int lq_backward_dispatch(const ProblemDesc& p, const GridDesc& g, int bat
     case LqMap::TwoWaves: run_lq_backward<LqM2, PW>(a, o.uconst, s); break;
     case LqMap::FourWaves: run_lq_backward<LqM4, PW>(a, o.uconst, s); break;
   }
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 int launch_backward_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
                        const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s) {
@@ -1860,7 +1860,7 @@ int launch_eval_lq(const ProblemDesc& p, int which, int k, const double* t, cons
                    const double* v, double* out, hipStream_t s) {
   if (p.W) return -1;   // k free columns have no trajectory index
   k_lq_eval<<<dim3((k + 127) / 128), dim3(128), 0, s>>>(which, k, p.nS, p.nC, t, y, u, v, p.ps, out);
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

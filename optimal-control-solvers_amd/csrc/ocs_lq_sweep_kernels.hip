@@ -158,7 +158,7 @@ int launch_sweep_forward_lq(const ProblemDesc& p, const GridDesc& g, int batch, 
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
   a.x0 = x0; a.u = u; a.x = x; a.J = J; a.frozen = frozen; a.gate = gate;
   lq_forward_one_wave(a, s);
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 int launch_sweep_costate_lq(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx,
@@ -172,7 +172,7 @@ int launch_sweep_costate_lq(const ProblemDesc& p, const GridDesc& g, int batch, 
     k_lq_sweep_costate<1><<<grid, block, 0, s>>>(a);
   else
     k_lq_sweep_costate<2><<<grid, block, 0, s>>>(a);
-  return hip_rc_lq(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

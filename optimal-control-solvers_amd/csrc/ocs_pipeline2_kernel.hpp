@@ -67,11 +67,9 @@ struct BufP2 {
   __device__ static inline BufP2 make(double* p) {
     return BufP2{__builtin_amdgcn_make_buffer_rsrc(p, 0, kNumRecP2, 0x00020000)};
   }
+  // plain (cached): the state rows of x, which the adjoint pass reads next (non-temporal and sc1 measured: NOTES.md)
   __device__ inline void st(double v, unsigned voff, unsigned soff) const {
-#ifndef OCS_P2_X_ST_AUX
-#define OCS_P2_X_ST_AUX 0   // cache policy of the state rows of x (tuning builds: scripts/build_variants.sh)
-#endif
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_p2, v), r, voff, soff, OCS_P2_X_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_p2, v), r, voff, soff, 0);
   }
   // non-temporal: for rows nobody reads back soon (the running-objective row: the adjoint pass reads the state rows only)
   __device__ inline void st_nt(double v, unsigned voff, unsigned soff) const {
@@ -218,7 +216,6 @@ __global__ __launch_bounds__((P2Cfg<P::NS, NKS, TPW_>::NWAVE * 64)) void k_forwa
     P2_END(0);
   } else if (wave == 1) {
     // ---------------- S: the recursion ----------------
-    chain_wave_priority();
     const int r = (lane / TPW) % G, tl = lane % TPW, b = bw + tl;   // (GS > G: the upper lane groups repeat the lower)
     const typename P::RowPar rp = P::load_row(ParamSrc{PS, a.pb, a.pmask, B, b}, r);
     const bool fz = FRZ && a.frozen != nullptr && a.frozen[b] != 0;

@@ -10,7 +10,6 @@
 
 namespace ocs {
 
-static inline int hip_rc7(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // ---------------------------------------------------------------------------------------
 bool pipeline_supported(Functor f, int nS, int nC);
@@ -42,13 +41,8 @@ int launch_forward_pv(const ProblemDesc& p, const GridDesc& g, int batch, const 
     void* args[] = {(void*)&a};
     return jit_launch(p.user, x ? UK_FWD_PV_X : UK_FWD_PV_J, dim3(tile_count(batch, 64)), dim3(kPvWaves * 64), args, s);
   }
-  switch (p.nS) {
-    case 1: run_forward_pv<LogisticK<1>>(a, s); break;
-    case 2: run_forward_pv<LogisticK<2>>(a, s); break;
-    case 3: run_forward_pv<LogisticK<3>>(a, s); break;
-    default: run_forward_pv<LogisticK<4>>(a, s); break;
-  }
-  return hip_rc7(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_forward_pv<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 template <class P, bool UNI>
@@ -91,14 +85,7 @@ int launch_forward_p2(const ProblemDesc& p, const GridDesc& g, int batch, const 
                       p.nS == 1 ? 0u : 48u * 1024u);
   }
   const FwdArgsP2 a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, frozen, no_cost_row ? 1 : 0, gate};
-  if (p.nS == 1)
-    run_forward_p2<LogisticK<1>>(a, g.uniform, s);
-  else if (p.nS == 2)
-    run_forward_p2<LogisticK<2>>(a, g.uniform, s);
-  else if (p.nS == 4)
-    run_forward_p2<LogisticK<4>>(a, g.uniform, s);
-  else
-    return -1;
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_forward_p2<decltype(P)>(a, g.uniform, s); })) return -1;
 #ifdef OCS_P2_STAMPS
   {
     static int calls = 0;
@@ -132,7 +119,7 @@ int launch_forward_p2(const ProblemDesc& p, const GridDesc& g, int batch, const 
     }
   }
 #endif
-  return hip_rc7(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

@@ -31,7 +31,6 @@
 
 namespace ocs {
 
-static inline int hip_rc5(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 template <int CTRL>
 __device__ static inline double dpp_quad_pl(double v) {
@@ -443,7 +442,6 @@ __global__ __launch_bounds__(128) void k_costate_pl(const CostateArgsPL a) {
     return;
   }
   // ---------------- L: costate recursion ----------------
-  chain_wave_priority();
   const int r = lane % G, tl = lane / G;
   const int b = bw + tl;
   const uniform_ptr PS = as_uniform(a.ps);
@@ -768,7 +766,6 @@ __global__ __launch_bounds__(MET ? 576 : 320) void k_costate_plx(const CostateXA
     return;
   }
   // ---------------- L: costate recursion ----------------
-  chain_wave_priority();
   const uniform_ptr PS = as_uniform(a.ps);
   const typename P::RowPar rp = P::load_row([&](int k) OCS_INLINE {
     return ((a.pmask >> k) & 1u) ? a.pb[(size_t)k * B + b] : PS[k];
@@ -847,15 +844,8 @@ int launch_costate_plx(const ProblemDesc& p, const GridDesc& g, int batch, const
   a.c = CostateArgsPL{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, nullptr, frozen, dump, lam};
   a.PR = PR;
   a.gate = gate;
-  if (p.nS == 1)
-    run_costate_plx<LogisticK<1>>(a, s);
-  else if (p.nS == 2)
-    run_costate_plx<LogisticK<2>>(a, s);
-  else if (p.nS == 4)
-    run_costate_plx<LogisticK<4>>(a, s);
-  else
-    return -1;
-  return hip_rc5(hipGetLastError());
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_costate_plx<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 // costate pass + change of the control + check_convergence (CostateXArgs, MET); lam holds the costate of the sweep before
@@ -870,15 +860,8 @@ int launch_costate_met(const ProblemDesc& p, const GridDesc& g, int batch, const
   const CostateXArgs a{CostateArgsPL{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, nullptr, status, nullptr, lam},
                        PR, gate, g.TU, lb, ub, relTol, absTol, sweep, status, maxChange, nactive};
   const dim3 grid(tile_count(batch, 64 / p.nS)), block(576);
-  if (p.nS == 1)
-    k_costate_plx<LogisticK<1>, true, true><<<grid, block, 0, s>>>(a);
-  else if (p.nS == 2)
-    k_costate_plx<LogisticK<2>, true, true><<<grid, block, 0, s>>>(a);
-  else if (p.nS == 4)
-    k_costate_plx<LogisticK<4>, true, true><<<grid, block, 0, s>>>(a);
-  else
-    return -1;
-  return hip_rc5(hipGetLastError());
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { k_costate_plx<decltype(P), true, true><<<grid, block, 0, s>>>(a); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 // (k_costate_pl / k_costate_plx move no control samples: they are only instantiated for registry problems whose
@@ -899,15 +882,8 @@ int launch_costate_pl(const ProblemDesc& p, const GridDesc& g, int batch, const 
                       const int* frozen, double* dump, double* lam, hipStream_t s) {
   if (!costate_pl_ok(p.functor, p.nS, p.nC, g.N, batch) || (frozen && !dump)) return -1;
   const CostateArgsPL a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x, ldx, xmid, frozen, dump, lam};
-  if (p.nS == 1)
-    run_costate_pl<LogisticK<1>>(a, s);
-  else if (p.nS == 2)
-    run_costate_pl<LogisticK<2>>(a, s);
-  else if (p.nS == 4)
-    run_costate_pl<LogisticK<4>>(a, s);
-  else
-    return -1;
-  return hip_rc5(hipGetLastError());
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_costate_pl<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------
@@ -947,15 +923,8 @@ int launch_backward_pl(const ProblemDesc& p, const GridDesc& g, int batch, const
                        hipStream_t s) {
   if (!pipeline_shape_ok(p.nS, g.N, batch, true) || (!lam && !dJdu)) return -1;
   BwdArgsPL a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, xck, u, lamT, lam, dJdu, lam0, pend0};
-  if (p.nS == 1)
-    run_backward_pl<LogisticK<1>>(a, s);
-  else if (p.nS == 2)
-    run_backward_pl<LogisticK<2>>(a, s);
-  else if (p.nS == 4)
-    run_backward_pl<LogisticK<4>>(a, s);
-  else
-    return -1;
-  return hip_rc5(hipGetLastError());
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_backward_pl<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

@@ -215,4 +215,11 @@ struct LogisticK {
   }
 };
 
+// Host: nS -> LogisticK<nS>, restricted to the SIZES a kernel is instantiated for.  f(LogisticK<nS>{}) runs for a size on the
+// list; any other size runs nothing and gives false (the launcher returns -1).  Use: [&](auto P) { run<decltype(P)>(...); }
+template <int... SIZES, class F>
+inline bool for_logistic(int nS, F&& f) {
+  return ((nS == SIZES ? (f(LogisticK<SIZES>{}), true) : false) || ...);
+}
+
 }  // namespace ocs

@@ -19,7 +19,6 @@
 
 namespace ocs {
 
-static inline int hip_rc4(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // fp64 cross-lane move inside a quad (DPP quad_perm on the two 32-bit halves)
 template <int CTRL>
@@ -342,13 +341,8 @@ static void run_forward_rs(const FwdArgsRS& a, hipStream_t s) {
 int launch_forward_rs(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                       double* x, double* J, hipStream_t s) {
   const FwdArgsRS a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J};
-  if (p.nS == 2)
-    run_forward_rs<LogisticK<2>>(a, s);
-  else if (p.nS == 4)
-    run_forward_rs<LogisticK<4>>(a, s);
-  else
-    return -1;
-  return hip_rc4(hipGetLastError());
+  if (!for_logistic<2, 4>(p.nS, [&](auto P) { run_forward_rs<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 template <class P>
@@ -366,13 +360,8 @@ int launch_backward_rs(const ProblemDesc& p, const GridDesc& g, int batch, const
                        const double* lamT, double* lam, double* dJdu, double* lam0, hipStream_t s) {
   if (!lam && !dJdu) return -1;
   const BwdArgsRS a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, xck, u, lamT, lam, dJdu, lam0};
-  if (p.nS == 2)
-    run_backward_rs<LogisticK<2>>(a, s);
-  else if (p.nS == 4)
-    run_backward_rs<LogisticK<4>>(a, s);
-  else
-    return -1;
-  return hip_rc4(hipGetLastError());
+  if (!for_logistic<2, 4>(p.nS, [&](auto P) { run_backward_rs<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

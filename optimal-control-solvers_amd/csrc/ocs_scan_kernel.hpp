@@ -115,19 +115,13 @@ struct Buf {
     return Buf{__builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p), 0, nrec, 0x00020000)};
   }
   __device__ inline double ld(unsigned voff, unsigned soff) const {
-#ifndef OCS_SCAN_LD_AUX
-#define OCS_SCAN_LD_AUX 0
-#endif
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, OCS_SCAN_LD_AUX));
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
   }
   __device__ inline void st0(double v, unsigned voff, unsigned soff) const {   // plain (cached) store
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_sc, v), r, voff, soff, 0);
   }
-  __device__ inline void st(double v, unsigned voff, unsigned soff) const {
-#ifndef OCS_SCAN_ST_AUX
-#define OCS_SCAN_ST_AUX 2   // nt: see the note on non-temporal stores at the top of the file
-#endif
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_sc, v), r, voff, soff, OCS_SCAN_ST_AUX);
+  __device__ inline void st(double v, unsigned voff, unsigned soff) const {   // non-temporal (aux 2; measured: NOTES.md)
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_sc, v), r, voff, soff, 2);
   }
 };
 // 16-byte-per-lane LDS-DMA: lane l copies src_l[0..1] to lds_base[2l..2l+1]
@@ -143,11 +137,7 @@ constexpr int kScanPadBack = 8;    // and after step N-1 (a wave copies 8 record
 // Checkpoints of a chunk's upper L - 1 steps integrated again from the first instead of read (k_backward_scan): 8 nS / L
 // bytes of checkpoint traffic per (trajectory, step) instead of 8 nS, for four more evaluations of the row's right-hand
 // side.  Measured at BL-2 (batch 4096, nS = 4): buffers that rotate through HBM 94.5 -> 89.2 us, one buffer set re-used
-// from the memory-side cache 79.9 -> 81.0 us; nS = 1: 70.3 -> 66.8 / 69.2 -> 66.7 us (profiles/r04f_xrc.log).
-#ifndef OCS_SCAN_XRC
-#define OCS_SCAN_XRC 1
-#endif
-constexpr bool kScanXRC = OCS_SCAN_XRC != 0;
+// from the memory-side cache 79.9 -> 81.0 us; nS = 1: 70.3 -> 66.8 / 69.2 -> 66.7 us (profiles/r04f_xrc.log; NOTES.md).
 
 // W waves per workgroup (chunks per superblock), L steps per chunk
 template <class P, int W, int L, bool OUT_LAM, bool OUT_DJDU, bool LT>
@@ -196,7 +186,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
   const unsigned vd_r0 = (G == 4 && r == 2) ? vd_bot : vd_r;                          // step q = 0
 
   struct Ld {
-    double x[L];          // x(r, lo+q)
+    double x0;            // x(r, lo): the checkpoint of the chunk's first step, the only one read (see above)
     double u[2 * L + 1];  // u(2 lo + k)
     double xb, ub0, ub1;  // DFDU_READS_Y only: x(r, lo-1), u(2 lo - 2), u(2 lo - 1) (stage state 4 of the step below)
   };
@@ -213,7 +203,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
     const int lr = lo >= 0 ? lo - 1 : -kScanPadFront;
     if (q == 0) dma16_sc(a.RECS + (long long)lr * kScanRec + 2 * lane, &rcs[slot][wave][0]);
     const Buf bx = Buf::make(a.xck + (size_t)lc * colB), bu = Buf::make(a.u + (size_t)(2 * lc) * B);
-    if (!kScanXRC || q == 0) d.x[q] = bx.ld(vx, (unsigned)q * col8);
+    if (q == 0) d.x0 = bx.ld(vx, 0);
     d.u[2 * q] = bu.ld(vu, (unsigned)(2 * q) * B8);
     d.u[2 * q + 1] = bu.ld(vu, (unsigned)(2 * q + 1) * B8);
     if (q == L - 1) d.u[2 * L] = bu.ld(vu, (unsigned)(2 * L) * B8);
@@ -248,12 +238,12 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
     const double* rw = &rcs[slot][wave][0];
     // ---------------- phase 1: stage states and the chunk map ----------------
-    // Steps in ascending order: (kScanXRC) only the checkpoint of the chunk's first step was read, the next one comes out
+    // Steps in ascending order: only the checkpoint of the chunk's first step was read, the next one comes out
     // of the stage evaluations the step map needs anyway plus one more right-hand side (RK4Integrator.m:49-50 on this row)
     // -- 8 nS / L instead of 8 nS bytes of checkpoint traffic per (trajectory, step).  The chunk map is composed from the
     // bottom: lam_lo = A lam_(above the steps so far) + Bq.
     double xs[L];
-    xs[0] = d.x[0];
+    xs[0] = d.x0;
     double A = 1.0, Bq = 0.0;
     // AFF: what phase 3 needs of step i = lo + q, as affine functions of lam_{i+1}, kept instead of the stage states:
     // lam_i (al, be), the midpoint column p23 (mp, mq), the k1 half of node column 2i (c1 kp, kq_i) and the k4 half of
@@ -272,12 +262,8 @@ __global__ __launch_bounds__(W * 64) void k_backward_scan(const BwdArgsScan a) {
       const double F3 = P::g_row_f(Y3, uM, c.tM, rp);
       const double Y4 = __builtin_fma(c.h, F3, xi);
       if (q + 1 < L) {
-        if (kScanXRC) {
-          const double F4 = P::g_row_f(Y4, uB, c.tB, rp);
-          xs[q + 1] = __builtin_fma(c.h6, ((F1 + 2.0 * F2) + 2.0 * F3) + F4, xi);   // :50
-        } else {
-          xs[q + 1] = d.x[q + 1];
-        }
+        const double F4 = P::g_row_f(Y4, uB, c.tB, rp);
+        xs[q + 1] = __builtin_fma(c.h6, ((F1 + 2.0 * F2) + 2.0 * F3) + F4, xi);   // :50
       }
       const Stage s4 = P::template stage<LT>(c.s4, c.h6, c.tB, lamc), s3 = P::template stage<LT>(c.s3, c.h3, c.tM, lamc),
                   s1 = P::template stage<LT>(c.s1, c.h6, c.tA, lamc);

@@ -10,7 +10,6 @@
 
 namespace ocs {
 
-static inline int hip_rc6(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // RECS points at the record of step 0
 __global__ void k_build_recs(int N, int RS, int SCO, const double* __restrict__ REC, double* __restrict__ RECS) {
@@ -32,7 +31,7 @@ size_t scan_recs_front() { return (size_t)kScanPadFront * kScanRec; }
 int launch_build_recs(int N, int rs, int sco, const double* REC, double* RECS_base, hipStream_t s) {
   const int n = N + kScanPadFront + kScanPadBack;
   k_build_recs<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(N, rs, sco, REC, RECS_base + (size_t)kScanPadFront * kScanRec);
-  return hip_rc6(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------
@@ -97,13 +96,8 @@ int launch_backward_vscan(const ProblemDesc& p, const GridDesc& g, int batch, co
     void* args[] = {(void*)&a};
     return jit_launch(p.user, kid, dim3((batch + 63) / 64), dim3(vscan_waves(p.nS) * 64), args, s);
   }
-  switch (p.nS) {
-    case 1: run_backward_vscan<LogisticK<1>>(a, s); break;
-    case 2: run_backward_vscan<LogisticK<2>>(a, s); break;
-    case 3: run_backward_vscan<LogisticK<3>>(a, s); break;
-    default: run_backward_vscan<LogisticK<4>>(a, s); break;
-  }
-  return hip_rc6(hipGetLastError());
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_backward_vscan<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------
@@ -120,6 +114,14 @@ bool costate_scan_ok(const ProblemDesc& p, const GridDesc& g, int batch) {
   if (p.functor == Functor::User) return user_fold(p.user) && shape;
   return !off && scan_supported(p.functor, p.nS, p.nC) && shape && (on || batch / (64 / p.nS) <= 128);
 }
+// what every costate scan reads and writes; the control samples and the MET fields stay zero
+static CostateScanArgs costate_scan_args(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx,
+                                         const double* PR, const int* frozen, double* lam, const int* gate) {
+  CostateScanArgs a{};
+  a.N = g.N; a.batch = batch; a.RECS = g.RECS; a.PR = PR; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
+  a.x = x; a.ldx = ldx; a.frozen = frozen; a.lam = lam; a.gate = gate;
+  return a;
+}
 template <class P, bool MET>
 static void run_costate_scan(const CostateScanArgs& a, hipStream_t s) {
   k_costate_scan<P, kScanW, kScanL, MET><<<dim3(tile_count(a.batch, 64 / P::NS)), dim3(kScanW * 64), 0, s>>>(a);
@@ -131,21 +133,13 @@ static int launch_costate_scan_t(const ProblemDesc& p, const CostateScanArgs& a,
     void* args[] = {(void*)&a};
     return jit_launch(p.user, UK_COSTATE_SCAN_MET, dim3(tile_count(a.batch, 64 / p.nS)), dim3(kScanW * 64), args, s);
   }
-  if (p.nS == 1)
-    run_costate_scan<LogisticK<1>, MET>(a, s);
-  else if (p.nS == 2)
-    run_costate_scan<LogisticK<2>, MET>(a, s);
-  else
-    run_costate_scan<LogisticK<4>, MET>(a, s);
-  return hip_rc6(hipGetLastError());
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_costate_scan<decltype(P), MET>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 int launch_costate_scan(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* PR,
                         const int* frozen, double* lam, hipStream_t s, const int* gate) {
   if (!costate_scan_ok(p, g, batch) || !PR) return -1;
-  CostateScanArgs a{};
-  a.N = g.N; a.batch = batch; a.RECS = g.RECS; a.PR = PR; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.x = x; a.ldx = ldx; a.frozen = frozen; a.lam = lam; a.gate = gate;
-  return launch_costate_scan_t<false>(p, a, s);
+  return launch_costate_scan_t<false>(p, costate_scan_args(p, g, batch, x, ldx, PR, frozen, lam, gate), s);
 }
 // any user problem given as row functions: the scan that reads the control samples (hipRTC instance)
 bool costate_scan_u_ok(const ProblemDesc& p, const GridDesc& g, int batch) {
@@ -155,9 +149,8 @@ bool costate_scan_u_ok(const ProblemDesc& p, const GridDesc& g, int batch) {
 int launch_costate_scan_u(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* PR,
                           const double* u, const int* frozen, double* lam, hipStream_t s, const int* gate) {
   if (!costate_scan_u_ok(p, g, batch) || !PR || !u) return -1;
-  CostateScanArgs a{};
-  a.N = g.N; a.batch = batch; a.RECS = g.RECS; a.PR = PR; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.x = x; a.ldx = ldx; a.frozen = frozen; a.lam = lam; a.gate = gate; a.u = u;
+  CostateScanArgs a = costate_scan_args(p, g, batch, x, ldx, PR, frozen, lam, gate);
+  a.u = u;
   void* args[] = {(void*)&a};
   return jit_launch(p.user, UK_COSTATE_SCAN_U, dim3(tile_count(batch, 64 / p.nS)), dim3(kScanW * 64), args, s);
 }
@@ -168,9 +161,8 @@ bool costate_vscan_ok(const ProblemDesc& p, const GridDesc& g, int batch) {
 int launch_costate_vscan(const ProblemDesc& p, const GridDesc& g, int batch, const double* x, int ldx, const double* PR,
                          const double* u, const int* frozen, double* lam, hipStream_t s, const int* gate) {
   if (!costate_vscan_ok(p, g, batch) || !PR || !u) return -1;
-  CostateScanArgs a{};
-  a.N = g.N; a.batch = batch; a.RECS = g.RECS; a.PR = PR; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.x = x; a.ldx = ldx; a.frozen = frozen; a.lam = lam; a.gate = gate; a.u = u;
+  CostateScanArgs a = costate_scan_args(p, g, batch, x, ldx, PR, frozen, lam, gate);
+  a.u = u;
   void* args[] = {(void*)&a};
   return jit_launch(p.user, UK_COSTATE_VSCAN, dim3((batch + 63) / 64), dim3(vscan_waves(p.nS) * 64), args, s);
 }
@@ -178,9 +170,7 @@ int launch_costate_scan_met(const ProblemDesc& p, const GridDesc& g, int batch, 
                             const double* lb, const double* ub, double relTol, double absTol, int sweep, int* status,
                             double* maxChange, int* nactive, double* lam, hipStream_t s, const int* gate) {
   if (!costate_scan_ok(p, g, batch) || !PR || !g.TU || !status || !maxChange || !nactive) return -1;
-  CostateScanArgs a{};
-  a.N = g.N; a.batch = batch; a.RECS = g.RECS; a.PR = PR; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.x = x; a.ldx = ldx; a.frozen = status; a.lam = lam; a.gate = gate;
+  CostateScanArgs a = costate_scan_args(p, g, batch, x, ldx, PR, status, lam, gate);   // (a frozen instance: status != 0)
   a.TU = g.TU; a.lb = lb; a.ub = ub; a.relTol = relTol; a.absTol = absTol; a.sweep = sweep; a.status = status;
   a.maxChange = maxChange; a.nactive = nactive;
   return launch_costate_scan_t<true>(p, a, s);
@@ -199,13 +189,8 @@ int launch_backward_scan(const ProblemDesc& p, const GridDesc& g, int batch, con
     void* args[] = {(void*)&a};
     return jit_launch(p.user, kid, dim3((batch + TPW - 1) / TPW), dim3(kScanW * 64), args, s);
   }
-  if (p.nS == 1)
-    run_backward_scan<LogisticK<1>>(a, s);
-  else if (p.nS == 2)
-    run_backward_scan<LogisticK<2>>(a, s);
-  else
-    run_backward_scan<LogisticK<4>>(a, s);
-  return hip_rc6(hipGetLastError());
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_backward_scan<decltype(P)>(a, s); })) return -1;
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

@@ -8,7 +8,6 @@
 
 namespace ocs {
 
-static inline int hip_rc6(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 __device__ static inline double spg_proj(double w, double lb, double ub) { return fmin(fmax(w, lb), ub); }
 
@@ -136,7 +135,7 @@ int launch_spg(int which, const SpgArgs& a, int it, double* pgnorm, int* converg
     case 4: k_spg_finish<<<grid, block, 0, s>>>(a, pgnorm, converged); break;
     default: return -1;
   }
-  return hip_rc6(hipGetLastError());
+  return hip_rc(hipGetLastError());
 }
 
 }  // namespace ocs

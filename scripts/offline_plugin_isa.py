@@ -1,6 +1,10 @@
 """Register / scratch / LDS use of the kernels a hipRTC plugin gets, compiled OFFLINE with hipcc the way csrc/ocs_jit.cpp
-assembles the program (no GPU needed): python scripts/offline_plugin_isa.py [ring6]  [kernel name expression ...]
-Writes /tmp/ocs_offline/<name>.s and prints .vgpr_count / scratch / LDS per kernel."""
+assembles the program (no GPU needed): python scripts/offline_plugin_isa.py [ring6 | predprey | logistic_rows]  [kernel name expression ...]
+  ring6          coupled, from symbols, past the vector mappings: the lane kernels
+  predprey       tests/user_problems.py PREDPREY_SRC, a full-vector plugin: the vector scans (k_backward_vscan, k_costate_vscan)
+  logistic_rows  LOGISTIC_ROWS_CC_SRC with two rows, a row-function plugin with ControlChar of the costate alone: k_forward_cc,
+                 k_costate_scan<MET>, k_backward_scan
+Writes <OUT_DIR, default /tmp/ocs_offline>/<name>.s and prints .vgpr_count / scratch / LDS per kernel."""
 import os, re, subprocess, sys, importlib.util
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 CSRC = os.path.join(ROOT, 'optimal-control-solvers_amd', 'csrc')
@@ -14,10 +18,29 @@ if which == "ring6":
     gg, f, vals = up.ring6_symbolic(sym)
     gen = sym.generate(gg, f, 6, 3, vals, [[0.0, 1.0]] * 3)
     nS, nC = 6, 3
+    default = ["ocs::k_costate<ocs::UserP, 4>", "ocs::k_control_grid<ocs::UserP>", "ocs::k_control_pts<ocs::UserP>",
+               "ocs::k_forward<ocs::UserP, 1, 4, true, false>", "ocs::k_backward<ocs::UserP, 1, 4, true, true, false>"]
+    includes = ""
+elif which == "predprey":   # the names ocs_jit.cpp asks for: W = 8 chunks of L = 4 steps at two states
+    nS, nC = 2, 1
+    gen = {"source": up.PREDPREY_SRC, "params": up.PREDPREY_PARAMS, "row_separable": False, "has_control_char": False,
+           "control_from_costate": False}
+    default = [f"ocs::k_backward_vscan<ocs::UserP, 8, 4, {o}, {lt}>" for o in ("true, true", "true, false", "false, true")
+               for lt in ("false", "true")] + ["ocs::k_costate_vscan<ocs::UserP, 8, 4>"]
+    includes = "ocs_pipelinev_kernel.hpp,ocs_vscan_kernel.hpp,ocs_costate_vscan_kernel.hpp"
+elif which == "logistic_rows":
+    nS, nC = 2, 1
+    gen = {"source": up.LOGISTIC_ROWS_CC_SRC, "params": [0.0] * (2 + nS), "row_separable": True, "has_control_char": True,
+           "control_from_costate": True}
+    default = ["ocs::k_forward_cc<ocs::UserP, true>", "ocs::k_forward_cc<ocs::UserP, false>",
+               "ocs::k_costate_scan<ocs::UserP, 16, 4, true>", "ocs::k_costate_scan<ocs::UserP, 16, 4, false, true>",
+               "ocs::k_forward_p2<ocs::UserP, true, true, false, 0>"] + \
+              [f"ocs::k_backward_scan<ocs::UserP, 16, 4, {o}, {lt}>" for o in ("true, true", "true, false", "false, true")
+               for lt in ("false", "true")]
+    includes = "ocs_pipeline2_kernel.hpp,ocs_scan_kernel.hpp,ocs_costate_scan_kernel.hpp,ocs_fold_kernel.hpp"
 else:
     raise SystemExit("unknown problem")
-kernels = sys.argv[2:] or ["ocs::k_costate<ocs::UserP, 4>", "ocs::k_control_grid<ocs::UserP>", "ocs::k_control_pts<ocs::UserP>",
-                           "ocs::k_forward<ocs::UserP, 1, 4, true, false>", "ocs::k_backward<ocs::UserP, 1, 4, true, true, false>"]
+kernels = sys.argv[2:] or default
 rowsep = bool(gen["row_separable"]); fold = rowsep and gen["has_control_char"] and gen["control_from_costate"]
 npar = len(gen["params"])
 src = "#include <hip/hip_runtime.h>\n"
@@ -29,16 +52,13 @@ src += '#include "ocs_device_common.hpp"\nconstexpr int NS = OCS_USER_NS, NC = O
 src += "typedef const double* OCS_PARAMS;\n" if (npar <= 16 and not rowsep) else "typedef ocs::uniform_ptr OCS_PARAMS;\n"
 src += gen["source"]
 src += '\n#include "ocs_user_functor.hpp"\n#include "ocs_rk4_kernels.hpp"\n#include "ocs_fbs_device.hpp"\n'
-for h in sys.argv[0:0]: pass
-extra = os.environ.get("EXTRA_INCLUDES", "")
+extra = os.environ.get("EXTRA_INCLUDES", includes)
 for h in extra.split(","):
     if h: src += f'#include "{h}"\n'
-for k in kernels:
-    src += f"template __global__ void {k}(" + "decltype(ocs::first_arg(&" + k + ")));\n" if False else ""
 # explicit instantiation needs the argument type: take the address instead
 for i, k in enumerate(kernels):
     src += f"auto* ocs_keep_{i} = &{k};\n"
-out = "/tmp/ocs_offline"; os.makedirs(out, exist_ok=True)
+out = os.environ.get("OUT_DIR", "/tmp/ocs_offline"); os.makedirs(out, exist_ok=True)
 path = os.path.join(out, f"{which}.hip")
 open(path, "w").write(src)
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", f"-I{CSRC}", "-S",
