@@ -78,6 +78,121 @@ __device__ static inline StepRec<NTC> load_rec(const double* q) {
   return r;
 }
 
+// Ring of PF prefetched step records, the one every lane kernel walks the table with.  `Rec rq[PF]` and the table pointer
+// `recp` are the caller's locals, and the caller fills the ring with its own loop (why: NOTES.md, "Lane RK4 kernels").
+// DIR is the direction of that loop and has to match it: +1 where it steps `recp += rec_stride(NTC)` up from step 0,
+// -1 where it steps `recp -= rec_stride(NTC)` down from step N-1.  rec_ring_next hands out the oldest record, rq[0], and
+// requests one more; until then rq[q] is the record that the q-th call from now returns.  The table is padded by kRecPad
+// records at either end, so the ring never clamps.  PF steps of lead, not one: a step is shorter than the L2 round trip
+// of a new record.
+template <int NTC, int PF, int DIR>
+__device__ inline OCS_INLINE StepRec<NTC> rec_ring_next(StepRec<NTC> (&rq)[PF], const double*& recp) {
+  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
+  static_assert(DIR == 1 || DIR == -1, "walking direction");
+  const StepRec<NTC> cur = rq[0];
+#pragma unroll
+  for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
+  rq[PF - 1] = load_rec<NTC>(recp);
+  recp += DIR * rec_stride(NTC);
+  return cur;
+}
+
+// ---------------------------------------------------------------------------------------
+// one RK4 step of a lane (= trajectory), forward and reverse: THE copy of the lane kernels' arithmetic
+// ---------------------------------------------------------------------------------------
+// compute_states, RK4Integrator.m:36-51: y (and the running objective yc) from node i to i+1, controls at grid points
+// 2i (uA), 2i+1 (uM), 2i+2 (uB).  COST = false is the same step on the state rows only (P::Fx; yc untouched): the
+// adjoint kernel's re-integration of checkpoints, which has to reproduce the state pass bit for bit.
+template <class P, bool COST = true>
+__device__ inline OCS_INLINE void lane_state_step(const StepRec<P::NTC>& r, double* y, double& yc, const double* uA,
+                                                  const double* uM, const double* uB, const typename P::Par& p) {
+  constexpr int NS = P::NS, NF = COST ? NS + 1 : NS;
+  auto rhs = [&](const double* tc, const double* x, const double* u, double* f) OCS_INLINE {
+    if constexpr (COST) P::F(tc, x, u, p, f);
+    else P::Fx(tc, x, u, p, f);
+  };
+  double F1[NF], F2[NF], F3[NF], F4[NF], Y[NS];
+  rhs(r.tcA, y, uA, F1);                                                 // :39
+#pragma unroll
+  for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F1[k], y[k]);  // :40
+  rhs(r.tcM, Y, uM, F2);                                                 // :42
+#pragma unroll
+  for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F2[k], y[k]);  // :43
+  rhs(r.tcM, Y, uM, F3);                                                 // :45
+#pragma unroll
+  for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.h, F3[k], y[k]);   // :46
+  rhs(r.tcB, Y, uB, F4);                                                 // :48
+#pragma unroll
+  for (int k = 0; k < NS; ++k)                                           // :50-51
+    y[k] = __builtin_fma(r.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
+  if constexpr (COST)
+    yc = __builtin_fma(r.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+}
+template <class P>
+__device__ inline OCS_INLINE void lane_state_rows_step(const StepRec<P::NTC>& r, double* y, const double* uA,
+                                                       const double* uM, const double* uB, const typename P::Par& p) {
+  double none = 0.0;
+  lane_state_step<P, false>(r, y, none, uA, uM, uB, p);
+}
+
+// compute_adjoints, RK4Integrator.m:73-88, with compute_dJdu :97-121 fused in: the reverse of step i from the checkpoint
+// xi = y_i.  lam(1:nS) is updated in place; lamc = lam(end,:) is constant (the last row of dFdx_times_vec is 0,
+// OCProblem.m:14-15).  With DJDU the two columns of dJdu that this step finishes are handed to columns(dn, dm) -- dn is
+// column 2i+2 (k4 of this step plus pend, the k1-term of step i+1), dm column 2i+1 -- before pend becomes this step's
+// k1-term and lam is updated: the caller stores or folds them at the place where every lane kernel always did (after
+// the step instead, the fused kernels spill).  Without DJDU the dFduT calls vanish and columns is never called.
+template <class P, bool DJDU, class Columns>
+__device__ inline OCS_INLINE void lane_adjoint_step(const StepRec<P::NTC>& r, const double* xi, const double* uA,
+                                                    const double* uM, const double* uB, const typename P::Par& p,
+                                                    double* lam, const double lamc, double* pend, Columns&& columns) {
+  constexpr int NS = P::NS, NC = P::NC, NAUG = P::NAUG;
+  // stage states xK(:,i,2:4), recomputed (compute_states :39-46)
+  double f[NS], Y2[NS], Y3[NS], Y4[NS];
+  P::Fx(r.tcA, xi, uA, p, f);
+#pragma unroll
+  for (int k = 0; k < NS; ++k) Y2[k] = __builtin_fma(r.hh, f[k], xi[k]);
+  P::Fx(r.tcM, Y2, uM, p, f);
+#pragma unroll
+  for (int k = 0; k < NS; ++k) Y3[k] = __builtin_fma(r.hh, f[k], xi[k]);
+  P::Fx(r.tcM, Y3, uM, p, f);
+#pragma unroll
+  for (int k = 0; k < NS; ++k) Y4[k] = __builtin_fma(r.h, f[k], xi[k]);
+  // dJdk(:,i,4..1) and the dJdx terms   :73-88
+  double k4[NAUG], k3[NAUG], k2[NAUG], k1[NAUG], g3[NS], g2[NS], g1[NS], g0[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) k4[k] = r.h6 * lam[k];                             // :73
+  k4[NS] = r.h6 * lamc;
+  P::dFdxT(r.tcB, Y4, uB, p, k4, g3);                                             // :74-75
+#pragma unroll
+  for (int k = 0; k < NS; ++k) k3[k] = __builtin_fma(r.h, g3[k], r.h3 * lam[k]);  // :77
+  k3[NS] = r.h3 * lamc;
+  P::dFdxT(r.tcM, Y3, uM, p, k3, g2);                                             // :78-79
+#pragma unroll
+  for (int k = 0; k < NS; ++k) k2[k] = __builtin_fma(r.hh, g2[k], r.h3 * lam[k]); // :81
+  k2[NS] = r.h3 * lamc;
+  P::dFdxT(r.tcM, Y2, uM, p, k2, g1);                                             // :82-83
+#pragma unroll
+  for (int k = 0; k < NS; ++k) k1[k] = __builtin_fma(r.hh, g1[k], r.h6 * lam[k]); // :85
+  k1[NS] = r.h6 * lamc;
+  P::dFdxT(r.tcA, xi, uA, p, k1, g0);                                             // :87-88
+  if constexpr (DJDU) {  // compute_dJdu :97-121: column 2i+2 pairs k4 of step i with k1 of step i+1
+    double d4[NC], d3[NC], d2[NC];
+    P::dFduT(r.tcB, Y4, uB, p, k4, d4);
+    P::dFduT(r.tcM, Y3, uM, p, k3, d3);
+    P::dFduT(r.tcM, Y2, uM, p, k2, d2);
+    double dn[NC], dm[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      dn[c] = pend[c] + d4[c];  // column 2i+2  :112-116 (:119-120 at i = N-1)
+      dm[c] = d2[c] + d3[c];    // column 2i+1  :105-109
+    }
+    columns(dn, dm);
+    P::dFduT(r.tcA, xi, uA, p, k1, pend);
+  }
+#pragma unroll
+  for (int k = 0; k < NS; ++k) lam[k] = (((lam[k] + g1[k]) + g2[k]) + g3[k]) + g0[k];  // :86-88
+}
+
 // pchip (Fritsch-Carlson / MATLAB pchipslopes) interior slope of a node between secants del0, del1 with weights w1, w2:
 // with ONE division: |del0 del1| / (w1 |del0| + w2 |del1|) (pchip_interior's harmonic mean multiplied
 // through by dmax; round-off level difference to the two-division form of the midpoint kernel)

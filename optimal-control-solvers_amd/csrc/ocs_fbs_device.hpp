@@ -311,14 +311,14 @@ __global__ __launch_bounds__(64) void k_costate(const CostateArgs a) {
     for (int k = 0; k < NS; ++k) out[k] = -g[k];
   };
 
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
-  Rec rq[PF];
-  const double* recp = a.REC + (size_t)(N - 1) * rec_stride(NTC);  // walks down; padded before step 0
+  Rec rq[PF];  // walks down; padded before step 0
+  const double* recp = a.REC + (size_t)(N - 1) * rec_stride(NTC);
 #pragma unroll
   for (int q = 0; q < PF; ++q) {
     rq[q] = load_rec<NTC>(recp);
     recp -= rec_stride(NTC);
   }
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, -1>(rq, recp); };
   // node/midpoint states and control samples are prefetched one chunk (CH steps) ahead, ping-pong
   auto step = [&](const Rec& r, int i, const double* cxA, const double* cxM, const double* cuA,
                   const double* cuM) OCS_INLINE {
@@ -344,14 +344,6 @@ __global__ __launch_bounds__(64) void k_costate(const CostateArgs a) {
     for (int c = 0; c < NC; ++c) uB[c] = cuA[c];
     lq -= NS * lrow;
     (void)i;
-  };
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec r = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp -= rec_stride(NTC);
-    return r;
   };
   // steps per prefetched chunk: two chunks of CH (2 NS + 2 NC) doubles are live at a time -- 8 steps for the small problems,
   // fewer as the state grows (8 steps of a six-state problem are 576 registers: the pass ran out of scratch memory at 3.4 ms

@@ -103,7 +103,6 @@ __global__ __launch_bounds__(64) void k_forward_fb(const FbArgs a) {
     c0.adv = 0;
     control(c0, uprev);
   }
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
   Rec rq[PF];
   const double* recp = a.REC;
 #pragma unroll
@@ -111,34 +110,35 @@ __global__ __launch_bounds__(64) void k_forward_fb(const FbArgs a) {
     rq[q] = load_rec<NTC>(recp);
     recp += rec_stride(NTC);
   }
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, 1>(rq, recp); };
   BandCol cM = band_col(CT, 1), cB = band_col(CT, 2);
   for (int i = 0; i < N; ++i) {
     // the next step's two columns are requested now (scalar loads) and used an iteration later
     const int jn = 2 * i + 3 <= 2 * N - 1 ? 2 * i + 3 : 2 * N - 1;
     const BandCol nM = band_col(CT, jn), nB2 = band_col(CT, jn + 1);
-    const Rec r_ = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp += rec_stride(NTC);
+    const Rec r_ = next_rec();
     double uM[NC], uB[NC];
     control(cM, uM);
     control(cB, uB);
-    double F1[NS + 1], F2[NS + 1], F3[NS + 1], F4[NS + 1], Y[NS];
-    P::F(r_.tcA, y, uprev, p, F1);                                          // :39
+    if constexpr (NS == 2) {  // written out: on the shared step this instance timed outside the parent's range (NOTES.md)
+      double F1[NS + 1], F2[NS + 1], F3[NS + 1], F4[NS + 1], Y[NS];
+      P::F(r_.tcA, y, uprev, p, F1);                                          // :39
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r_.hh, F1[k], y[k]);  // :40
-    P::F(r_.tcM, Y, uM, p, F2);                                             // :42
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r_.hh, F1[k], y[k]);  // :40
+      P::F(r_.tcM, Y, uM, p, F2);                                             // :42
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r_.hh, F2[k], y[k]);  // :43
-    P::F(r_.tcM, Y, uM, p, F3);                                             // :45
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r_.hh, F2[k], y[k]);  // :43
+      P::F(r_.tcM, Y, uM, p, F3);                                             // :45
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r_.h, F3[k], y[k]);   // :46
-    P::F(r_.tcB, Y, uB, p, F4);                                             // :48
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r_.h, F3[k], y[k]);   // :46
+      P::F(r_.tcB, Y, uB, p, F4);                                             // :48
 #pragma unroll
-    for (int k = 0; k < NS; ++k)                                            // :50-51
-      y[k] = __builtin_fma(r_.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
-    yc = __builtin_fma(r_.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+      for (int k = 0; k < NS; ++k)                                            // :50-51
+        y[k] = __builtin_fma(r_.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
+      yc = __builtin_fma(r_.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+    } else {
+      lane_state_step<P>(r_, y, yc, uprev, uM, uB, p);
+    }
 #pragma unroll
     for (int k = 0; k < NS; ++k) xo[(size_t)k * B] = y[k];
     xo += (size_t)NAUG * B;
@@ -234,7 +234,6 @@ __global__ __launch_bounds__(64) void k_backward_fb(const FbArgs a) {
   for (int c = 0; c < NC; ++c) pend[c] = 0.0;
   int adv_g = 0;  // adv of the column above the one cursor G folds next (0 for the very first column, 2N)
 
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
   Rec rq[PF];
   const double* recp = a.REC + (size_t)(N - 1) * rec_stride(NTC);
 #pragma unroll
@@ -242,6 +241,7 @@ __global__ __launch_bounds__(64) void k_backward_fb(const FbArgs a) {
     rq[q] = load_rec<NTC>(recp);
     recp -= rec_stride(NTC);
   }
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, -1>(rq, recp); };
   BandCol cM = band_col(CT, 2 * N - 1), cA = band_col(CT, 2 * N - 2);
   // checkpoints are requested four steps ahead into a ring of four slots; the loop is unrolled by the ring so that
   // no freshly requested value is copied (a copy would be a wait)
@@ -262,58 +262,63 @@ __global__ __launch_bounds__(64) void k_backward_fb(const FbArgs a) {
 #pragma unroll
     for (int k = 0; k < NS; ++k) xi[k] = xslot[k];
     load_x(i - RD, xslot);
-    const Rec r = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp -= rec_stride(NTC);
+    const Rec r = next_rec();
 
     double uA[NC], uM[NC];
     control_down(cTop.adv, cM.w0, cM.w1, uM);  // column 2i+1 (the band may drop between 2i+2 and 2i+1)
     control_down(cM.adv, cA.w0, cA.w1, uA);    // column 2i
-    const double* uB = unext;
-    double f[NS], Y2[NS], Y3[NS], Y4[NS];
-    P::Fx(r.tcA, xi, uA, p, f);
+    if constexpr (NS == 2) {  // written out: on the shared step this instance timed outside the parent's range (NOTES.md)
+      const double* uB = unext;
+      double f[NS], Y2[NS], Y3[NS], Y4[NS];
+      P::Fx(r.tcA, xi, uA, p, f);
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y2[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y2, uM, p, f);
+      for (int k = 0; k < NS; ++k) Y2[k] = __builtin_fma(r.hh, f[k], xi[k]);
+      P::Fx(r.tcM, Y2, uM, p, f);
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y3[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y3, uM, p, f);
+      for (int k = 0; k < NS; ++k) Y3[k] = __builtin_fma(r.hh, f[k], xi[k]);
+      P::Fx(r.tcM, Y3, uM, p, f);
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y4[k] = __builtin_fma(r.h, f[k], xi[k]);
-    double k4[NAUG], k3[NAUG], k2[NAUG], k1[NAUG], g3[NS], g2[NS], g1[NS], g0[NS];
+      for (int k = 0; k < NS; ++k) Y4[k] = __builtin_fma(r.h, f[k], xi[k]);
+      double k4[NAUG], k3[NAUG], k2[NAUG], k1[NAUG], g3[NS], g2[NS], g1[NS], g0[NS];
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k4[k] = r.h6 * lam[k];                             // :73
-    k4[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcB, Y4, uB, p, k4, g3);                                             // :74-75
+      for (int k = 0; k < NS; ++k) k4[k] = r.h6 * lam[k];                             // :73
+      k4[NS] = r.h6 * lamc;
+      P::dFdxT(r.tcB, Y4, uB, p, k4, g3);                                             // :74-75
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k3[k] = __builtin_fma(r.h, g3[k], r.h3 * lam[k]);  // :77
-    k3[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y3, uM, p, k3, g2);                                             // :78-79
+      for (int k = 0; k < NS; ++k) k3[k] = __builtin_fma(r.h, g3[k], r.h3 * lam[k]);  // :77
+      k3[NS] = r.h3 * lamc;
+      P::dFdxT(r.tcM, Y3, uM, p, k3, g2);                                             // :78-79
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k2[k] = __builtin_fma(r.hh, g2[k], r.h3 * lam[k]); // :81
-    k2[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y2, uM, p, k2, g1);                                             // :82-83
+      for (int k = 0; k < NS; ++k) k2[k] = __builtin_fma(r.hh, g2[k], r.h3 * lam[k]); // :81
+      k2[NS] = r.h3 * lamc;
+      P::dFdxT(r.tcM, Y2, uM, p, k2, g1);                                             // :82-83
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k1[k] = __builtin_fma(r.hh, g1[k], r.h6 * lam[k]); // :85
-    k1[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcA, xi, uA, p, k1, g0);                                             // :87-88
-    double d4[NC], d3[NC], d2[NC], dn[NC], dm[NC];
-    P::dFduT(r.tcB, Y4, uB, p, k4, d4);
-    P::dFduT(r.tcM, Y3, uM, p, k3, d3);
-    P::dFduT(r.tcM, Y2, uM, p, k2, d2);
+      for (int k = 0; k < NS; ++k) k1[k] = __builtin_fma(r.hh, g1[k], r.h6 * lam[k]); // :85
+      k1[NS] = r.h6 * lamc;
+      P::dFdxT(r.tcA, xi, uA, p, k1, g0);                                             // :87-88
+      double d4[NC], d3[NC], d2[NC], dn[NC], dm[NC];
+      P::dFduT(r.tcB, Y4, uB, p, k4, d4);
+      P::dFduT(r.tcM, Y3, uM, p, k3, d3);
+      P::dFduT(r.tcM, Y2, uM, p, k2, d2);
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      dn[c] = pend[c] + d4[c];  // column 2i+2  :112-116 (:119-120 at i = N-1)
-      dm[c] = d2[c] + d3[c];    // column 2i+1  :105-109
+      for (int c = 0; c < NC; ++c) {
+        dn[c] = pend[c] + d4[c];  // column 2i+2  :112-116 (:119-120 at i = N-1)
+        dm[c] = d2[c] + d3[c];    // column 2i+1  :105-109
+      }
+      fold(adv_g, cTop.w0, cTop.w1, dn);
+      fold(cTop.adv, cM.w0, cM.w1, dm);
+      adv_g = cM.adv;
+      P::dFduT(r.tcA, xi, uA, p, k1, pend);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) lam[k] = (((lam[k] + g1[k]) + g2[k]) + g3[k]) + g0[k];  // :86-88
+    } else {
+      lane_adjoint_step<P, true>(r, xi, uA, uM, unext, p, lam, lamc, pend,
+                               [&](const double (&dn)[NC], const double (&dm)[NC]) OCS_INLINE {
+        fold(adv_g, cTop.w0, cTop.w1, dn);
+        fold(cTop.adv, cM.w0, cM.w1, dm);
+        adv_g = cM.adv;
+      });
     }
-    fold(adv_g, cTop.w0, cTop.w1, dn);
-    fold(cTop.adv, cM.w0, cM.w1, dm);
-    adv_g = cM.adv;
-    P::dFduT(r.tcA, xi, uA, p, k1, pend);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) lam[k] = (((lam[k] + g1[k]) + g2[k]) + g3[k]) + g0[k];  // :86-88
 #pragma unroll
     for (int c = 0; c < NC; ++c) unext[c] = uA[c];
     cTop = cA;
@@ -362,18 +367,24 @@ static int launch_fb(bool forward, const ProblemDesc& p, const FbArgs& a, hipStr
   if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_fb<decltype(P)>(forward, a, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
-int launch_forward_fb(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, int r0, const double* CT,
-                      const double* v, const double* x0, double* ck, double* J, hipStream_t s) {
+// the fields both directions share
+static FbArgs fb_args(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, int r0, const double* CT,
+                      const double* v, const double* ck) {
   FbArgs a{};
   a.N = g.N; a.batch = batch; a.nBasis = nBasis; a.r0 = r0; a.REC = g.REC; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.CT = CT; a.v = v; a.x0 = x0; a.ck = ck; a.J = J;
+  a.CT = CT; a.v = v; a.ck = const_cast<double*>(ck);
+  return a;
+}
+int launch_forward_fb(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, int r0, const double* CT,
+                      const double* v, const double* x0, double* ck, double* J, hipStream_t s) {
+  FbArgs a = fb_args(p, g, batch, nBasis, r0, CT, v, ck);
+  a.x0 = x0; a.J = J;
   return launch_fb(true, p, a, s);
 }
 int launch_backward_fb(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, int r0, const double* CT,
                        const double* v, const double* ck, double* dJdv, double* lam0, hipStream_t s) {
-  FbArgs a{};
-  a.N = g.N; a.batch = batch; a.nBasis = nBasis; a.r0 = r0; a.REC = g.REC; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.CT = CT; a.v = v; a.ck = const_cast<double*>(ck); a.dJdv = dJdv; a.lam0 = lam0;
+  FbArgs a = fb_args(p, g, batch, nBasis, r0, CT, v, ck);
+  a.dJdv = dJdv; a.lam0 = lam0;
   return launch_fb(false, p, a, s);
 }
 

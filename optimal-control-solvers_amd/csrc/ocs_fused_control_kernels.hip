@@ -121,6 +121,15 @@ __device__ static inline void fc_load_v(const FcArgs& a, size_t B, int b, double
       }
 }
 
+// u(:,j) = sum_k v_k B(k,j) from the lane's entries row[0..NG) of basis column j   ChebyshevControl.m:35-39
+template <int NC, int NG>
+__device__ static inline void fc_control(const double* row, const double (&vv)[NG][16][NC], double (&u)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) u[c] = 0.0;
+#pragma unroll
+  for (int g = 0; g < NG; ++g) FcRow16<NC>::dot(row[g], vv[g], u);
+}
+
 // ---------------------------------------------------------------------------------------
 // J = x(end,end) of compute_states(u = v*B)   RK4Integrator.m:28-56, checkpoints y_i kept for the adjoint
 // ---------------------------------------------------------------------------------------
@@ -138,12 +147,7 @@ __global__ __launch_bounds__(64) void k_forward_fc(const FcArgs a) {
 
   double vv[NG][16][NC];
   fc_load_v<P, NG>(a, B, b, vv);
-  auto u_of = [&](const double (&row)[NG], double (&u)[NC]) OCS_INLINE {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) u[c] = 0.0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) FcRow16<NC>::dot(row[g], vv[g], u);
-  };
+  auto u_of = [&](const double (&row)[NG], double (&u)[NC]) OCS_INLINE { fc_control<NC, NG>(row, vv, u); };
 
   double y[NS], yc = 0.0;
 #pragma unroll
@@ -167,27 +171,30 @@ __global__ __launch_bounds__(64) void k_forward_fc(const FcArgs a) {
   }
 
   auto step = [&](const Rec& r, const double* uA, const double* uM, const double* uB) OCS_INLINE {
-    double F1[NS + 1], F2[NS + 1], F3[NS + 1], F4[NS + 1], Y[NS];
-    P::F(r.tcA, y, uA, p, F1);                                             // :39
+    if constexpr (NS == 1 && NG == 2) {  // written out: on the shared step this instance timed outside the parent's range (NOTES.md)
+      double F1[NS + 1], F2[NS + 1], F3[NS + 1], F4[NS + 1], Y[NS];
+      P::F(r.tcA, y, uA, p, F1);                                             // :39
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F1[k], y[k]);  // :40
-    P::F(r.tcM, Y, uM, p, F2);                                             // :42
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F1[k], y[k]);  // :40
+      P::F(r.tcM, Y, uM, p, F2);                                             // :42
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F2[k], y[k]);  // :43
-    P::F(r.tcM, Y, uM, p, F3);                                             // :45
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F2[k], y[k]);  // :43
+      P::F(r.tcM, Y, uM, p, F3);                                             // :45
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.h, F3[k], y[k]);   // :46
-    P::F(r.tcB, Y, uB, p, F4);                                             // :48
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.h, F3[k], y[k]);   // :46
+      P::F(r.tcB, Y, uB, p, F4);                                             // :48
 #pragma unroll
-    for (int k = 0; k < NS; ++k)                                           // :50-51
-      y[k] = __builtin_fma(r.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
-    yc = __builtin_fma(r.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+      for (int k = 0; k < NS; ++k)                                           // :50-51
+        y[k] = __builtin_fma(r.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
+      yc = __builtin_fma(r.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+    } else {
+      lane_state_step<P>(r, y, yc, uA, uM, uB, p);
+    }
 #pragma unroll
     for (int k = 0; k < NS; ++k) xo[(size_t)k * B] = y[k];  // the cost row of a checkpoint is never read
     xo += (size_t)NAUG * B;
   };
 
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
   Rec rq[PF];
   const double* recp = a.REC;
 #pragma unroll
@@ -195,15 +202,7 @@ __global__ __launch_bounds__(64) void k_forward_fc(const FcArgs a) {
     rq[q] = load_rec<NTC>(recp);
     recp += rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp += rec_stride(NTC);
-    return cur;
-  };
-
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, 1>(rq, recp); };
   // basis columns are prefetched one chunk (CH steps = 2 CH columns) ahead, ping-pong in registers
   double rb0[2 * CH][NG], rb1[2 * CH][NG];
   auto load_chunk = [&](double (&dst)[2 * CH][NG]) OCS_INLINE {
@@ -270,12 +269,7 @@ __global__ __launch_bounds__(64) void k_backward_fc(const FcArgs a) {
     for (int k = 0; k < 16; ++k)
 #pragma unroll
       for (int c = 0; c < NC; ++c) gv[g][k][c] = 0.0;
-  auto u_of = [&](const double (&row)[NG], double (&u)[NC]) OCS_INLINE {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) u[c] = 0.0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) FcRow16<NC>::dot(row[g], vv[g], u);
-  };
+  auto u_of = [&](const double (&row)[NG], double (&u)[NC]) OCS_INLINE { fc_control<NC, NG>(row, vv, u); };
   auto fold = [&](const double (&row)[NG], const double (&d)[NC]) OCS_INLINE {  // dJdv += dJdu(:,j) B(:,j)'
 #pragma unroll
     for (int g = 0; g < NG; ++g) FcRow16<NC>::axpy(row[g], d, gv[g]);
@@ -303,57 +297,18 @@ __global__ __launch_bounds__(64) void k_backward_fc(const FcArgs a) {
     double uA[NC], uM[NC];
     u_of(rA, uA);
     u_of(rM, uM);
-    const double* uB = unext;
-    double f[NS], Y2[NS], Y3[NS], Y4[NS];
-    P::Fx(r.tcA, xi, uA, p, f);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y2[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y2, uM, p, f);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y3[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y3, uM, p, f);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y4[k] = __builtin_fma(r.h, f[k], xi[k]);
-    double k4[NAUG], k3[NAUG], k2[NAUG], k1[NAUG], g3[NS], g2[NS], g1[NS], g0[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k4[k] = r.h6 * lam[k];                             // :73
-    k4[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcB, Y4, uB, p, k4, g3);                                             // :74-75
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k3[k] = __builtin_fma(r.h, g3[k], r.h3 * lam[k]);  // :77
-    k3[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y3, uM, p, k3, g2);                                             // :78-79
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k2[k] = __builtin_fma(r.hh, g2[k], r.h3 * lam[k]); // :81
-    k2[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y2, uM, p, k2, g1);                                             // :82-83
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k1[k] = __builtin_fma(r.hh, g1[k], r.h6 * lam[k]); // :85
-    k1[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcA, xi, uA, p, k1, g0);                                             // :87-88
-    // compute_dJdu :97-121: column 2i+2 pairs k4 of step i with k1 of step i+1; both columns are folded
-    // into dJdv at once
-    double d4[NC], d3[NC], d2[NC], dn[NC], dm[NC];
-    P::dFduT(r.tcB, Y4, uB, p, k4, d4);
-    P::dFduT(r.tcM, Y3, uM, p, k3, d3);
-    P::dFduT(r.tcM, Y2, uM, p, k2, d2);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      dn[c] = pend[c] + d4[c];  // column 2i+2  :112-116 (:119-120 at i = N-1)
-      dm[c] = d2[c] + d3[c];    // column 2i+1  :105-109
-    }
-    fold(rnext, dn);
-    fold(rM, dm);
-    P::dFduT(r.tcA, xi, uA, p, k1, pend);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) lam[k] = (((lam[k] + g1[k]) + g2[k]) + g3[k]) + g0[k];  // :86-88
+    // both finished columns of dJdu are folded into dJdv at once
+    lane_adjoint_step<P, true>(r, xi, uA, uM, unext, p, lam, lamc, pend,
+                               [&](const double (&dn)[NC], const double (&dm)[NC]) OCS_INLINE {
+      fold(rnext, dn);
+      fold(rM, dm);
+    });
 #pragma unroll
     for (int c = 0; c < NC; ++c) unext[c] = uA[c];
 #pragma unroll
     for (int g = 0; g < NG; ++g) rnext[g] = rA[g];
   };
 
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
   Rec rq[PF];
   const double* recp = a.REC + (size_t)(N - 1) * rec_stride(NTC);
 #pragma unroll
@@ -361,14 +316,7 @@ __global__ __launch_bounds__(64) void k_backward_fc(const FcArgs a) {
     rq[q] = load_rec<NTC>(recp);
     recp -= rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp -= rec_stride(NTC);
-    return cur;
-  };
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, -1>(rq, recp); };
   auto load_x = [&](double (&xi)[NS]) OCS_INLINE {
     xp -= (size_t)NAUG * B;
 #pragma unroll
@@ -443,6 +391,19 @@ __global__ __launch_bounds__(64) void k_backward_fc(const FcArgs a) {
 constexpr int kFc2Steps = 8;  // steps per block
 __device__ static inline void fc2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// the basis wave's half of a block: the NR samples u(:,j) of the basis columns src[0..NR) into one LDS slot
+template <int NC, int NR>
+__device__ static inline void fc2_expand(const double (&src)[NR], const double (&vv)[1][16][NC], double (&dst)[NR][NC][64],
+                                         const int lane) {
+#pragma unroll
+  for (int s = 0; s < NR; ++s) {
+    double u[NC];
+    fc_control<NC, 1>(&src[s], vv, u);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) dst[s][c][lane] = u[c];
+  }
+}
+
 template <class P>
 __global__ __launch_bounds__(128) void k_forward_fc2(const FcArgs a) {
   constexpr int NS = P::NS, NC = P::NC, NTC = P::NTC, NAUG = P::NAUG, LD = 16, BS = kFc2Steps, NR = 2 * BS;
@@ -465,21 +426,11 @@ __global__ __launch_bounds__(128) void k_forward_fc2(const FcArgs a) {
       for (int s = 0; s < NR; ++s) dst[s] = bp[s * LD];
       bp += NR * LD;
     };
-    auto expand = [&](const double (&src)[NR], const int slot) OCS_INLINE {
-#pragma unroll
-      for (int s = 0; s < NR; ++s) {
-        double u[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) u[c] = 0.0;
-        FcRow16<NC>::dot(src[s], vv[0], u);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) ub[slot][s][c][lane] = u[c];
-      }
-    };
+    auto expand = [&](const double (&src)[NR], const int slot) OCS_INLINE { fc2_expand<NC, NR>(src, vv, ub[slot], lane); };
     {
       const double r0 = bp[0];
       bp += LD;
-      double u[NC];
+      double u[NC];  // (fc_control on the address of this one value changes the code of both roles)
 #pragma unroll
       for (int c = 0; c < NC; ++c) u[c] = 0.0;
       FcRow16<NC>::dot(r0, vv[0], u);
@@ -515,27 +466,30 @@ __global__ __launch_bounds__(128) void k_forward_fc2(const FcArgs a) {
   for (int k = 0; k < NS; ++k) xo[(size_t)k * B] = y[k];
   xo += (size_t)NAUG * B;
   auto step = [&](const Rec& r, const double* uA, const double* uM, const double* uB) OCS_INLINE {
-    double F1[NS + 1], F2[NS + 1], F3[NS + 1], F4[NS + 1], Y[NS];
-    P::F(r.tcA, y, uA, p, F1);                                             // :39
+    if constexpr (NS == 2) {  // written out: on the shared step this instance timed outside the parent's range (NOTES.md)
+      double F1[NS + 1], F2[NS + 1], F3[NS + 1], F4[NS + 1], Y[NS];
+      P::F(r.tcA, y, uA, p, F1);                                             // :39
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F1[k], y[k]);  // :40
-    P::F(r.tcM, Y, uM, p, F2);                                             // :42
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F1[k], y[k]);  // :40
+      P::F(r.tcM, Y, uM, p, F2);                                             // :42
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F2[k], y[k]);  // :43
-    P::F(r.tcM, Y, uM, p, F3);                                             // :45
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F2[k], y[k]);  // :43
+      P::F(r.tcM, Y, uM, p, F3);                                             // :45
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.h, F3[k], y[k]);   // :46
-    P::F(r.tcB, Y, uB, p, F4);                                             // :48
+      for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.h, F3[k], y[k]);   // :46
+      P::F(r.tcB, Y, uB, p, F4);                                             // :48
 #pragma unroll
-    for (int k = 0; k < NS; ++k)                                           // :50-51
-      y[k] = __builtin_fma(r.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
-    yc = __builtin_fma(r.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+      for (int k = 0; k < NS; ++k)                                           // :50-51
+        y[k] = __builtin_fma(r.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
+      yc = __builtin_fma(r.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+    } else {
+      lane_state_step<P>(r, y, yc, uA, uM, uB, p);
+    }
 #pragma unroll
     for (int k = 0; k < NS; ++k) xo[(size_t)k * B] = y[k];
     xo += (size_t)NAUG * B;
   };
   constexpr int PF = 4;
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
   Rec rq[PF];
   const double* recp = a.REC;
 #pragma unroll
@@ -543,14 +497,7 @@ __global__ __launch_bounds__(128) void k_forward_fc2(const FcArgs a) {
     rq[q] = load_rec<NTC>(recp);
     recp += rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp += rec_stride(NTC);
-    return cur;
-  };
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, 1>(rq, recp); };
   fc2_barrier();
   double uprev[NC];
 #pragma unroll
@@ -603,17 +550,7 @@ __global__ __launch_bounds__(128) void k_backward_fc2(const FcArgs a) {
 #pragma unroll
       for (int s = 0; s < NR; ++s) dst[s] = q[s * LD];
     };
-    auto expand = [&](const double (&src)[NR], const int slot) OCS_INLINE {
-#pragma unroll
-      for (int s = 0; s < NR; ++s) {
-        double u[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) u[c] = 0.0;
-        FcRow16<NC>::dot(src[s], vv[0], u);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) ub[slot][s][c][lane] = u[c];
-      }
-    };
+    auto expand = [&](const double (&src)[NR], const int slot) OCS_INLINE { fc2_expand<NC, NR>(src, vv, ub[slot], lane); };
     auto contract = [&](const double (&src)[NR], const int slot) OCS_INLINE {  // the order of k_backward_fc: columns downwards
 #pragma unroll
       for (int s = NR - 1; s >= 0; --s) {
@@ -625,7 +562,7 @@ __global__ __launch_bounds__(128) void k_backward_fc2(const FcArgs a) {
     };
     {
       const double rt = bt[(size_t)(2 * N) * LD];
-      double u[NC];
+      double u[NC];  // (fc_control on the address of this one value changes the code of both roles)
 #pragma unroll
       for (int c = 0; c < NC; ++c) u[c] = 0.0;
       FcRow16<NC>::dot(rt, vv[0], u);
@@ -683,52 +620,62 @@ __global__ __launch_bounds__(128) void k_backward_fc2(const FcArgs a) {
 
   auto step = [&](const Rec& r, const double* xi, const double* uA, const double* uM, double (&dn)[NC],
                   double (&dm)[NC]) OCS_INLINE {
-    const double* uB = unext;
-    double f[NS], Y2[NS], Y3[NS], Y4[NS];
-    P::Fx(r.tcA, xi, uA, p, f);
+    if constexpr (NS == 2) {  // written out: on the shared step this instance timed outside the parent's range (NOTES.md)
+      const double* uB = unext;
+      double f[NS], Y2[NS], Y3[NS], Y4[NS];
+      P::Fx(r.tcA, xi, uA, p, f);
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y2[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y2, uM, p, f);
+      for (int k = 0; k < NS; ++k) Y2[k] = __builtin_fma(r.hh, f[k], xi[k]);
+      P::Fx(r.tcM, Y2, uM, p, f);
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y3[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y3, uM, p, f);
+      for (int k = 0; k < NS; ++k) Y3[k] = __builtin_fma(r.hh, f[k], xi[k]);
+      P::Fx(r.tcM, Y3, uM, p, f);
 #pragma unroll
-    for (int k = 0; k < NS; ++k) Y4[k] = __builtin_fma(r.h, f[k], xi[k]);
-    double k4[NAUG], k3[NAUG], k2[NAUG], k1[NAUG], g3[NS], g2[NS], g1[NS], g0[NS];
+      for (int k = 0; k < NS; ++k) Y4[k] = __builtin_fma(r.h, f[k], xi[k]);
+      double k4[NAUG], k3[NAUG], k2[NAUG], k1[NAUG], g3[NS], g2[NS], g1[NS], g0[NS];
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k4[k] = r.h6 * lam[k];                             // :73
-    k4[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcB, Y4, uB, p, k4, g3);                                             // :74-75
+      for (int k = 0; k < NS; ++k) k4[k] = r.h6 * lam[k];                             // :73
+      k4[NS] = r.h6 * lamc;
+      P::dFdxT(r.tcB, Y4, uB, p, k4, g3);                                             // :74-75
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k3[k] = __builtin_fma(r.h, g3[k], r.h3 * lam[k]);  // :77
-    k3[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y3, uM, p, k3, g2);                                             // :78-79
+      for (int k = 0; k < NS; ++k) k3[k] = __builtin_fma(r.h, g3[k], r.h3 * lam[k]);  // :77
+      k3[NS] = r.h3 * lamc;
+      P::dFdxT(r.tcM, Y3, uM, p, k3, g2);                                             // :78-79
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k2[k] = __builtin_fma(r.hh, g2[k], r.h3 * lam[k]); // :81
-    k2[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y2, uM, p, k2, g1);                                             // :82-83
+      for (int k = 0; k < NS; ++k) k2[k] = __builtin_fma(r.hh, g2[k], r.h3 * lam[k]); // :81
+      k2[NS] = r.h3 * lamc;
+      P::dFdxT(r.tcM, Y2, uM, p, k2, g1);                                             // :82-83
 #pragma unroll
-    for (int k = 0; k < NS; ++k) k1[k] = __builtin_fma(r.hh, g1[k], r.h6 * lam[k]); // :85
-    k1[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcA, xi, uA, p, k1, g0);                                             // :87-88
-    double d4[NC], d3[NC], d2[NC];
-    P::dFduT(r.tcB, Y4, uB, p, k4, d4);
-    P::dFduT(r.tcM, Y3, uM, p, k3, d3);
-    P::dFduT(r.tcM, Y2, uM, p, k2, d2);
+      for (int k = 0; k < NS; ++k) k1[k] = __builtin_fma(r.hh, g1[k], r.h6 * lam[k]); // :85
+      k1[NS] = r.h6 * lamc;
+      P::dFdxT(r.tcA, xi, uA, p, k1, g0);                                             // :87-88
+      double d4[NC], d3[NC], d2[NC];
+      P::dFduT(r.tcB, Y4, uB, p, k4, d4);
+      P::dFduT(r.tcM, Y3, uM, p, k3, d3);
+      P::dFduT(r.tcM, Y2, uM, p, k2, d2);
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      dn[c] = pend[c] + d4[c];  // column 2i+2  :112-116 (:119-120 at i = N-1)
-      dm[c] = d2[c] + d3[c];    // column 2i+1  :105-109
+      for (int c = 0; c < NC; ++c) {
+        dn[c] = pend[c] + d4[c];  // column 2i+2  :112-116 (:119-120 at i = N-1)
+        dm[c] = d2[c] + d3[c];    // column 2i+1  :105-109
+      }
+      P::dFduT(r.tcA, xi, uA, p, k1, pend);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) lam[k] = (((lam[k] + g1[k]) + g2[k]) + g3[k]) + g0[k];  // :86-88
+    } else {
+      lane_adjoint_step<P, true>(r, xi, uA, uM, unext, p, lam, lamc, pend,
+                               [&](const double (&n)[NC], const double (&m)[NC]) OCS_INLINE {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          dn[c] = n[c];
+          dm[c] = m[c];
+        }
+      });
     }
-    P::dFduT(r.tcA, xi, uA, p, k1, pend);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) lam[k] = (((lam[k] + g1[k]) + g2[k]) + g3[k]) + g0[k];  // :86-88
 #pragma unroll
     for (int c = 0; c < NC; ++c) unext[c] = uA[c];
   };
 
   constexpr int PF = 4;
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
   Rec rq[PF];
   const double* recp = a.REC + (size_t)(N - 1) * rec_stride(NTC);
 #pragma unroll
@@ -736,14 +683,7 @@ __global__ __launch_bounds__(128) void k_backward_fc2(const FcArgs a) {
     rq[q] = load_rec<NTC>(recp);
     recp -= rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp -= rec_stride(NTC);
-    return cur;
-  };
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, -1>(rq, recp); };
   auto load_xs = [&](double (&xd)[BS][NS]) OCS_INLINE {  // the checkpoints of one block, top first
 #pragma unroll
     for (int s = BS - 1; s >= 0; --s) {
@@ -843,19 +783,24 @@ static int launch_fc(bool forward, const ProblemDesc& p, const FcArgs& a, hipStr
   if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { two ? run_fc<decltype(P), 2>(forward, a, s) : run_fc<decltype(P), 1>(forward, a, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
-// BT16: transposed basis [2N+1][16 or 32] zero-padded (16 when nBasis <= 16)
-int launch_forward_fc(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, const double* BT16,
-                      const double* v, const double* x0, double* ck, double* J, hipStream_t s) {
+// the fields both directions share.  BT16: transposed basis [2N+1][16 or 32] zero-padded (16 when nBasis <= 16)
+static FcArgs fc_args(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, const double* BT16,
+                      const double* v, const double* ck) {
   FcArgs a{};
   a.N = g.N; a.batch = batch; a.nBasis = nBasis; a.REC = g.REC; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.BT = BT16; a.v = v; a.x0 = x0; a.ck = ck; a.J = J;
+  a.BT = BT16; a.v = v; a.ck = const_cast<double*>(ck);
+  return a;
+}
+int launch_forward_fc(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, const double* BT16,
+                      const double* v, const double* x0, double* ck, double* J, hipStream_t s) {
+  FcArgs a = fc_args(p, g, batch, nBasis, BT16, v, ck);
+  a.x0 = x0; a.J = J;
   return launch_fc(true, p, a, s);
 }
 int launch_backward_fc(const ProblemDesc& p, const GridDesc& g, int batch, int nBasis, const double* BT16,
                        const double* v, const double* ck, double* dJdv, double* lam0, hipStream_t s) {
-  FcArgs a{};
-  a.N = g.N; a.batch = batch; a.nBasis = nBasis; a.REC = g.REC; a.ps = p.ps; a.pb = p.pb; a.pmask = p.pmask;
-  a.BT = BT16; a.v = v; a.ck = const_cast<double*>(ck); a.dJdv = dJdv; a.lam0 = lam0;
+  FcArgs a = fc_args(p, g, batch, nBasis, BT16, v, ck);
+  a.dJdv = dJdv; a.lam0 = lam0;
   return launch_fc(false, p, a, s);
 }
 

@@ -128,23 +128,9 @@ __global__ __launch_bounds__(64) void k_forward(const FwdArgs a) {
     }
   }
 
-  // one RK4 step, controls at grid points 2i (uA), 2i+1 (uM), 2i+2 (uB)   :36-51
+  // one RK4 step (lane_state_step, ocs_device_common.hpp) and the stores of its node
   auto step = [&](const Rec& r, const double* uA, const double* uM, const double* uB) OCS_INLINE {
-    double F1[NS + 1], F2[NS + 1], F3[NS + 1], F4[NS + 1], Y[NS];
-    P::F(r.tcA, y, uA, p, F1);                                             // :39
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F1[k], y[k]);  // :40
-    P::F(r.tcM, Y, uM, p, F2);                                             // :42
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F2[k], y[k]);  // :43
-    P::F(r.tcM, Y, uM, p, F3);                                             // :45
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.h, F3[k], y[k]);   // :46
-    P::F(r.tcB, Y, uB, p, F4);                                             // :48
-#pragma unroll
-    for (int k = 0; k < NS; ++k)                                           // :50-51
-      y[k] = __builtin_fma(r.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
-    yc = __builtin_fma(r.h6, __builtin_fma(2.0, F3[NS], __builtin_fma(2.0, F2[NS], F1[NS])) + F4[NS], yc);
+    lane_state_step<P>(r, y, yc, uA, uM, uB, p);
     if (OUT_X) {
 #pragma unroll
       for (int k = 0; k < NS; ++k) {
@@ -168,24 +154,14 @@ __global__ __launch_bounds__(64) void k_forward(const FwdArgs a) {
         up += B;
       }
   };
-  // uniform step records are fetched PF steps ahead (scalar loads miss the scalar cache on
-  // every new 64-byte record, so one step of lead does not cover the L2 round trip)
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
-  Rec rq[PF];
-  const double* recp = REC;  // walks forward one record per step; the table is padded past step N-1
+  Rec rq[PF];  // walks forward one record per step; the table is padded past step N-1
+  const double* recp = REC;
 #pragma unroll
   for (int q = 0; q < PF; ++q) {
     rq[q] = load_rec<NTC>(recp);
     recp += rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp += rec_stride(NTC);
-    return cur;
-  };
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, 1>(rq, recp); };
   auto run_chunk = [&](const double (&src)[2 * CH][NC]) OCS_INLINE {
 #pragma unroll
     for (int s = 0; s < CH; ++s) {
@@ -317,54 +293,19 @@ __global__ __launch_bounds__(64) void k_backward(const BwdArgs a) {
 
   // reverse of RK4 step i: xi = y_i (checkpoint), controls uA (2i), uM (2i+1), uB (2i+2)
   auto step = [&](const Rec& r, const double* xi, const double* uA, const double* uM, const double* uB) OCS_INLINE {
-    // stage states xK(:,i,2:4), recomputed (compute_states :39-46)
-    double f[NS], Y2[NS], Y3[NS], Y4[NS];
-    P::Fx(r.tcA, xi, uA, p, f);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y2[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y2, uM, p, f);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y3[k] = __builtin_fma(r.hh, f[k], xi[k]);
-    P::Fx(r.tcM, Y3, uM, p, f);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Y4[k] = __builtin_fma(r.h, f[k], xi[k]);
-    // dJdk(:,i,4..1) and the dJdx terms   :73-88
-    double k4[NAUG], k3[NAUG], k2[NAUG], k1[NAUG], g3[NS], g2[NS], g1[NS], g0[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k4[k] = r.h6 * lam[k];                             // :73
-    k4[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcB, Y4, uB, p, k4, g3);                                             // :74-75
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k3[k] = __builtin_fma(r.h, g3[k], r.h3 * lam[k]);  // :77
-    k3[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y3, uM, p, k3, g2);                                             // :78-79
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k2[k] = __builtin_fma(r.hh, g2[k], r.h3 * lam[k]); // :81
-    k2[NS] = r.h3 * lamc;
-    P::dFdxT(r.tcM, Y2, uM, p, k2, g1);                                             // :82-83
-#pragma unroll
-    for (int k = 0; k < NS; ++k) k1[k] = __builtin_fma(r.hh, g1[k], r.h6 * lam[k]); // :85
-    k1[NS] = r.h6 * lamc;
-    P::dFdxT(r.tcA, xi, uA, p, k1, g0);                                             // :87-88
-    if (OUT_DJDU) {  // compute_dJdu :97-121, fused: column 2i+2 pairs k4 of step i with k1 of step i+1
-      double d4[NC], d3[NC], d2[NC];
-      P::dFduT(r.tcB, Y4, uB, p, k4, d4);
-      P::dFduT(r.tcM, Y3, uM, p, k3, d3);
-      P::dFduT(r.tcM, Y2, uM, p, k2, d2);
+    lane_adjoint_step<P, OUT_DJDU>(r, xi, uA, uM, uB, p, lam, lamc, pend,
+                               [&](const double* dn, const double* dm) OCS_INLINE {
 #pragma unroll
       for (int c = NC - 1; c >= 0; --c) {
         dp -= B;
-        OCS_LANE_ST(dp, pend[c] + d4[c]);  // column 2i+2  :112-116 (:119-120 at i = N-1)
+        OCS_LANE_ST(dp, dn[c]);  // column 2i+2
       }
 #pragma unroll
       for (int c = NC - 1; c >= 0; --c) {
         dp -= B;
-        OCS_LANE_ST(dp, d2[c] + d3[c]);    // column 2i+1  :105-109
+        OCS_LANE_ST(dp, dm[c]);  // column 2i+1
       }
-      P::dFduT(r.tcA, xi, uA, p, k1, pend);
-    }
-#pragma unroll
-    for (int k = 0; k < NS; ++k) lam[k] = (((lam[k] + g1[k]) + g2[k]) + g3[k]) + g0[k];  // :86-88
+    });
     if (OUT_LAM) {
       lo -= B;
       OCS_LANE_ST(lo, lamc);
@@ -377,22 +318,14 @@ __global__ __launch_bounds__(64) void k_backward(const BwdArgs a) {
   };
 
   const int nch = UCONST ? 0 : N / CH;
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
-  Rec rq[PF];
-  const double* recp = REC + (size_t)(N - 1) * rec_stride(NTC);  // walks down; padded before step 0
+  Rec rq[PF];  // walks down; padded before step 0
+  const double* recp = REC + (size_t)(N - 1) * rec_stride(NTC);
 #pragma unroll
   for (int q = 0; q < PF; ++q) {
     rq[q] = load_rec<NTC>(recp);
     recp -= rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp -= rec_stride(NTC);
-    return cur;
-  };
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, -1>(rq, recp); };
   // remainder steps at the top of the grid first (i = N-1 .. nch*CH), direct loads
   for (int i = N - 1; i >= nch * CH; --i) {
     double xi[NS], uA[NC], uM[NC];
@@ -454,22 +387,10 @@ __global__ __launch_bounds__(64) void k_backward(const BwdArgs a) {
 #pragma unroll
     for (int s = 1; s < CH; ++s) {
       if (XRC) {   // x(:, i0 + s) from x(:, i0 + s - 1): compute_states :39-51 on the state rows, the state pass's operations
-        const Rec& r = rq[CH - s];   // the ring holds the records of steps i0 + CH - 1 (rq[0]) .. i0 (rq[CH - 1])
-        const double *y = xs[s - 1], *uA = us[2 * s - 2], *uM = us[2 * s - 1], *uB = us[2 * s];
-        double F1[NS], F2[NS], F3[NS], F4[NS], Y[NS];
-        P::Fx(r.tcA, y, uA, p, F1);
+        // the ring holds the records of steps i0 + CH - 1 (rq[0]) .. i0 (rq[CH - 1])
 #pragma unroll
-        for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F1[k], y[k]);
-        P::Fx(r.tcM, Y, uM, p, F2);
-#pragma unroll
-        for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.hh, F2[k], y[k]);
-        P::Fx(r.tcM, Y, uM, p, F3);
-#pragma unroll
-        for (int k = 0; k < NS; ++k) Y[k] = __builtin_fma(r.h, F3[k], y[k]);
-        P::Fx(r.tcB, Y, uB, p, F4);
-#pragma unroll
-        for (int k = 0; k < NS; ++k)
-          xs[s][k] = __builtin_fma(r.h6, __builtin_fma(2.0, F3[k], __builtin_fma(2.0, F2[k], F1[k])) + F4[k], y[k]);
+        for (int k = 0; k < NS; ++k) xs[s][k] = xs[s - 1][k];
+        lane_state_rows_step<P>(rq[CH - s], xs[s], us[2 * s - 2], us[2 * s - 1], us[2 * s], p);
       } else {
 #pragma unroll
         for (int k = 0; k < NS; ++k) xs[s][k] = xs0[s][k];

@@ -97,22 +97,14 @@ __global__ __launch_bounds__(64) void k_forward_rs(const FwdArgsRS a) {
     }
   };
 
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
-  Rec rq[PF];
-  const double* recp = a.REC;  // walks forward one record per step; the table is padded past step N-1
+  Rec rq[PF];  // walks forward one record per step; the table is padded past step N-1
+  const double* recp = a.REC;
 #pragma unroll
   for (int q = 0; q < PF; ++q) {
     rq[q] = load_rec<NTC>(recp);
     recp += rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp += rec_stride(NTC);
-    return cur;
-  };
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, 1>(rq, recp); };
   double ub0[2 * CH], ub1[2 * CH];
   auto load_chunk = [&](double (&dst)[2 * CH]) OCS_INLINE {
 #pragma unroll
@@ -247,23 +239,14 @@ __global__ __launch_bounds__(64) void k_backward_rs(const BwdArgsRS a) {
     }
   };
 
-  static_assert(PF <= kRecPad, "record ring deeper than the table padding");
-  Rec rq[PF];
-  const double* recp = a.REC + (size_t)(N - 1) * rec_stride(NTC);  // walks down; padded before step 0
+  Rec rq[PF];  // walks down; padded before step 0
+  const double* recp = a.REC + (size_t)(N - 1) * rec_stride(NTC);
 #pragma unroll
   for (int q = 0; q < PF; ++q) {
     rq[q] = load_rec<NTC>(recp);
     recp -= rec_stride(NTC);
   }
-  auto next_rec = [&]() OCS_INLINE {
-    const Rec cur = rq[0];
-#pragma unroll
-    for (int q = 0; q + 1 < PF; ++q) rq[q] = rq[q + 1];
-    rq[PF - 1] = load_rec<NTC>(recp);
-    recp -= rec_stride(NTC);
-    return cur;
-  };
-
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, -1>(rq, recp); };
   const int nch = N / CH;
   for (int i = N - 1; i >= nch * CH; --i) {  // remainder steps at the top, direct loads
     xp -= colB;
