@@ -5,6 +5,8 @@
 #include "ocs_trace.hpp"
 #include "ocs_handles.hpp"
 
+#include <memory>
+
 using namespace ocs;
 
 // ------------------------------------------------------------------------------------
@@ -40,62 +42,45 @@ int ocs_problem_create(ocs_problem* out, int problem_id, int nS, int nC, const d
                        const double* control_bounds) {
   if (!out || !params || !control_bounds) return fail(OCS_ERR_INVALID, "null argument");
   *out = nullptr;
-  ocs_problem_s* p = new ocs_problem_s();
+  std::unique_ptr<ocs_problem_s> p(new ocs_problem_s());
   p->id = problem_id;
   p->nS = nS;
   p->nC = nC;
   if (problem_id == OCS_PROBLEM_TEST) {
     // tests/TestOCProblem.m:16-20, params [c m r] -> LogisticK<1> block [c r m]
-    if (nS != 1 || nC != 1 || nparams != 3) {
-      delete p;
+    if (nS != 1 || nC != 1 || nparams != 3)
       return fail(OCS_ERR_SHAPE, "TestOCProblem needs nS=1, nC=1, params [c m r]");
-    }
     p->functor = Functor::Logistic;
     p->par = {params[0], params[2], params[1]};
     p->user2func = {0, 2, 1};
   } else if (problem_id == OCS_PROBLEM_LOGISTIC) {
-    if (nS < 1 || nC != 1 || nparams != 2 + nS) {
-      delete p;
+    if (nS < 1 || nC != 1 || nparams != 2 + nS)
       return fail(OCS_ERR_SHAPE, "LogisticK needs nC=1 and params [c r m_1..m_nS]");
-    }
     p->functor = Functor::Logistic;
     p->par.assign(params, params + nparams);
     p->user2func.resize(nparams);
     for (int k = 0; k < nparams; ++k) p->user2func[k] = k;
   } else if (problem_id == OCS_PROBLEM_LQ) {
     // build-defined linear-quadratic problem: params [r | A | Bu | q | rdiag]
-    if (nS < 1 || nC < 1 || nparams != 1 + nS * nS + nS * nC + nS + nC) {
-      delete p;
+    if (nS < 1 || nC < 1 || nparams != 1 + nS * nS + nS * nC + nS + nC)
       return fail(OCS_ERR_SHAPE, "LQ needs params [r | A (nS x nS) | Bu (nS x nC) | q (nS) | rdiag (nC)]");
-    }
     p->functor = Functor::LQ;
     p->par.assign(params, params + nparams);
     p->user2func.resize(nparams);
     for (int k = 0; k < nparams; ++k) p->user2func[k] = k;
   } else {
-    delete p;
     return fail(OCS_ERR_UNSUPPORTED, "unknown problem id %d", problem_id);
   }
-  if (!functor_supported(p->functor, nS, nC)) {
-    delete p;
+  if (!functor_supported(p->functor, nS, nC))
     return fail(OCS_ERR_UNSUPPORTED, "no kernel instantiated for nS=%d nC=%d", nS, nC);
-  }
   p->bounds.assign(control_bounds, control_bounds + 2 * nC);
   p->version = next_version();
-  *out = p;
+  *out = p.release();
   return OCS_OK;
 }
 
 int ocs_problem_destroy(ocs_problem p) {
-  if (!p) return OCS_OK;
-  if (p->shadow) ocs_problem_destroy(p->shadow);
-  if (p->user) jit_free(p->user);
-  p->d_ps.release();
-  p->d_pb.release();
-  p->d_w.release();
-  p->d_lb.release();
-  p->d_ub.release();
-  delete p;
+  delete p;   // (~ocs_problem_s: the shadow problem and the hipRTC module, then the buffers)
   return OCS_OK;
 }
 
@@ -179,28 +164,18 @@ static int eval_common(ocs_problem p, int which, int k, const double* t, const d
   const int nAug = p->nS + 1, nC = p->nC;
   const int nout = (which == 2) ? nC : nAug;
   DevBuf dt, dy, du, dv, dout;
-  int rc = OCS_OK;
-  auto body = [&]() -> int {
-    OCS_TRY(dt.ensure(sizeof(double) * k));
-    OCS_TRY(dy.ensure(sizeof(double) * (size_t)nAug * k));
-    OCS_TRY(du.ensure(sizeof(double) * (size_t)nC * k));
-    OCS_TRY(dv.ensure(sizeof(double) * (size_t)nAug * k));
-    OCS_TRY(dout.ensure(sizeof(double) * (size_t)nout * k));
-    HIP_TRY(hipMemcpy(dt.p, t, sizeof(double) * k, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * (size_t)nAug * k, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du.p, u, sizeof(double) * (size_t)nC * k, hipMemcpyHostToDevice));
-    if (which != 0) HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * (size_t)nAug * k, hipMemcpyHostToDevice));
-    LAUNCH_TRY(launch_eval(describe(p), which, k, dt.d(), dy.d(), du.d(), dv.d(), dout.d(), nullptr));
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * (size_t)nout * k, hipMemcpyDeviceToHost));
-    return OCS_OK;
-  };
-  rc = body();
-  dt.release();
-  dy.release();
-  du.release();
-  dv.release();
-  dout.release();
-  return rc;
+  OCS_TRY(dt.ensure(sizeof(double) * k));
+  OCS_TRY(dy.ensure(sizeof(double) * (size_t)nAug * k));
+  OCS_TRY(du.ensure(sizeof(double) * (size_t)nC * k));
+  OCS_TRY(dv.ensure(sizeof(double) * (size_t)nAug * k));
+  OCS_TRY(dout.ensure(sizeof(double) * (size_t)nout * k));
+  HIP_TRY(hipMemcpy(dt.p, t, sizeof(double) * k, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dy.p, y, sizeof(double) * (size_t)nAug * k, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(du.p, u, sizeof(double) * (size_t)nC * k, hipMemcpyHostToDevice));
+  if (which != 0) HIP_TRY(hipMemcpy(dv.p, v, sizeof(double) * (size_t)nAug * k, hipMemcpyHostToDevice));
+  LAUNCH_TRY(launch_eval(describe(p), which, k, dt.d(), dy.d(), du.d(), dv.d(), dout.d(), nullptr));
+  HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * (size_t)nout * k, hipMemcpyDeviceToHost));
+  return OCS_OK;
 }
 int ocs_problem_F(ocs_problem p, int k, const double* t, const double* y, const double* u, double* out) {
   return eval_common(p, 0, k, t, y, u, nullptr, out);
@@ -244,37 +219,26 @@ int ocs_compute_equilibrium(ocs_problem p, int batch, double r, const double* yG
   const int n = 2 * p->nS + p->nC;
   const size_t nb = (size_t)n * batch;
   DevBuf dg, dl, du, dy, dr, dres, df, dst;
-  auto body = [&]() -> int {
-    OCS_TRY(dst.ensure(sizeof(double) * nb));
-    OCS_TRY(dg.ensure(sizeof(double) * nb));
-    OCS_TRY(dy.ensure(sizeof(double) * nb));
-    OCS_TRY(dres.ensure(sizeof(double) * nb));
-    OCS_TRY(dl.ensure(sizeof(double) * n));
-    OCS_TRY(du.ensure(sizeof(double) * n));
-    OCS_TRY(dr.ensure(sizeof(double) * batch));
-    OCS_TRY(df.ensure(sizeof(int) * batch));
-    HIP_TRY(hipMemcpy(dst.p, yGuess, sizeof(double) * nb, hipMemcpyHostToDevice));
-    LAUNCH_TRY(launch_to_batch_minor(dst.d(), dg.d(), n, batch, nullptr));
-    HIP_TRY(hipMemcpy(dl.p, lb, sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du.p, ub, sizeof(double) * n, hipMemcpyHostToDevice));
-    OCS_TRY(ocs_compute_equilibrium_dev(p, batch, r, dg.d(), dl.d(), du.d(), dy.d(), dr.d(), dres.d(), (int*)df.p,
-                                        nullptr));
-    LAUNCH_TRY(launch_to_traj_major(dy.d(), dst.d(), n, batch, nullptr));
-    HIP_TRY(hipMemcpy(y, dst.p, sizeof(double) * nb, hipMemcpyDeviceToHost));
-    if (residual) {
-      LAUNCH_TRY(launch_to_traj_major(dres.d(), dst.d(), n, batch, nullptr));
-      HIP_TRY(hipMemcpy(residual, dst.p, sizeof(double) * nb, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(hipMemcpy(resnorm, dr.p, sizeof(double) * batch, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(exitflag, df.p, sizeof(int) * batch, hipMemcpyDeviceToHost));
-    for (int b = 0; b < batch; ++b)
-      if (exitflag[b] < 0) return OCS_NUM_NONFINITE;   // (a numerical condition: the outputs of the other instances stand)
-    return OCS_OK;
-  };
-  const int rc = body();
-  DevBuf* all[] = {&dg, &dl, &du, &dy, &dr, &dres, &df, &dst};
-  for (DevBuf* q : all) q->release();
-  return rc;
+  OCS_TRY(dst.ensure(sizeof(double) * nb));
+  OCS_TRY(dg.ensure(sizeof(double) * nb));
+  OCS_TRY(dy.ensure(sizeof(double) * nb));
+  OCS_TRY(dres.ensure(sizeof(double) * nb));
+  OCS_TRY(dl.ensure(sizeof(double) * n));
+  OCS_TRY(du.ensure(sizeof(double) * n));
+  OCS_TRY(dr.ensure(sizeof(double) * batch));
+  OCS_TRY(df.ensure(sizeof(int) * batch));
+  HIP_TRY(hipMemcpy(dst.p, yGuess, sizeof(double) * nb, hipMemcpyHostToDevice));
+  LAUNCH_TRY(launch_to_batch_minor(dst.d(), dg.d(), n, batch, nullptr));
+  HIP_TRY(hipMemcpy(dl.p, lb, sizeof(double) * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(du.p, ub, sizeof(double) * n, hipMemcpyHostToDevice));
+  OCS_TRY(ocs_compute_equilibrium_dev(p, batch, r, dg.d(), dl.d(), du.d(), dy.d(), dr.d(), dres.d(), (int*)df.p, nullptr));
+  OCS_TRY(stage_out(dst, dy.d(), y, n, batch, nullptr));
+  if (residual) OCS_TRY(stage_out(dst, dres.d(), residual, n, batch, nullptr));
+  HIP_TRY(hipMemcpy(resnorm, dr.p, sizeof(double) * batch, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(exitflag, df.p, sizeof(int) * batch, hipMemcpyDeviceToHost));
+  for (int b = 0; b < batch; ++b)
+    if (exitflag[b] < 0) return OCS_NUM_NONFINITE;   // (a numerical condition: the outputs of the other instances stand)
+  return OCS_OK;
 }
 
 // ------------------------------------------------------------------------------------
@@ -284,7 +248,7 @@ int ocs_rk4_create(ocs_integrator* out, const double* tspan, int npts) {
   if (!out || !tspan) return fail(OCS_ERR_INVALID, "null argument");
   *out = nullptr;
   if (npts < 2) return fail(OCS_ERR_SHAPE, "tspan needs at least 2 points");
-  ocs_integrator_s* g = new ocs_integrator_s();
+  std::unique_ptr<ocs_integrator_s> g(new ocs_integrator_s());
   const int N = npts - 1;
   g->N = N;
   g->tspan.assign(tspan, tspan + npts);
@@ -294,11 +258,8 @@ int ocs_rk4_create(ocs_integrator* out, const double* tspan, int npts) {
   for (int i = 0; i <= N; ++i) g->t[2 * (size_t)i] = tspan[i];                    // :22
   for (int i = 0; i < N; ++i) g->t[2 * (size_t)i + 1] = (tspan[i] + tspan[i + 1]) / 2;  // :23
   for (int i = 0; i < N; ++i)
-    if (!(g->h[i] > 0) || !std::isfinite(g->h[i])) {
-      delete g;
-      return fail(OCS_ERR_INVALID, "tspan must be finite and strictly increasing");
-    }
-  *out = g;
+    if (!(g->h[i] > 0) || !std::isfinite(g->h[i])) return fail(OCS_ERR_INVALID, "tspan must be finite and strictly increasing");
+  *out = g.release();
   return OCS_OK;
 }
 
@@ -310,34 +271,17 @@ int ocs_rk4inf_create(ocs_integrator* out, const double* tspan, int npts, const 
   if (nC < 1) return fail(OCS_ERR_SHAPE, "uStar needs nC >= 1 entries");
   ocs_integrator g1 = nullptr, g2 = nullptr;
   OCS_TRY(ocs_rk4_create(&g1, tspan, npts));
-  int rc = ocs_rk4_create(&g2, tspanExtra, nptsExtra);
-  if (rc < 0) {
-    ocs_integrator_destroy(g1);
-    return rc;
-  }
-  g1->kind = 1;
-  g1->leg2 = g2;
-  g1->ustar.assign(uStar, uStar + nC);
-  *out = g1;
+  std::unique_ptr<ocs_integrator_s> leg1(g1);
+  OCS_TRY(ocs_rk4_create(&g2, tspanExtra, nptsExtra));
+  leg1->kind = 1;
+  leg1->leg2 = g2;
+  leg1->ustar.assign(uStar, uStar + nC);
+  *out = leg1.release();
   return OCS_OK;
 }
 
 int ocs_integrator_destroy(ocs_integrator g) {
-  if (g && g->tc_event) (void)hipEventDestroy(g->tc_event);
-  if (!g) return OCS_OK;
-  if (g->leg2) ocs_integrator_destroy(g->leg2);
-  if (g->fbs) ocs_fbs_state_free(g->fbs);
-  if (g->lqws) lq_workspace_free(g->lqws);
-  g->d_ustar.release();
-  g->d_lam2.release();
-  g->d_utail.release();
-  g->d_lamtail.release();
-  g->d_J2.release();
-  if (g->stream) (void)hipStreamDestroy(g->stream);
-  DevBuf* bufs[] = {&g->d_HT, &g->d_T, &g->d_TC, &g->d_TU, &g->d_REC, &g->d_RECS, &g->d_split, &g->d_x0, &g->d_u, &g->d_x, &g->d_J,
-                    &g->d_lam, &g->d_dJdu, &g->d_lamT, &g->d_stage, &g->d_ck};
-  for (DevBuf* b : bufs) b->release();
-  delete g;
+  delete g;   // (~ocs_integrator_s: event, tail leg, sweep and LQ workspaces, stream, then the buffers)
   return OCS_OK;
 }
 int ocs_integrator_set_mapping(ocs_integrator g, int mapping) {
@@ -467,24 +411,6 @@ int ocs_compute_adjoints_dev(ocs_integrator g, ocs_problem p, int batch, const d
   return OCS_OK;
 }
 
-// host staging: MATLAB-shaped host array (per doubles per trajectory, trajectory-major) -> batch-minor
-static int stage_in(ocs_integrator_s* g, const double* host, DevBuf& dst, int per, int batch) {
-  const size_t bytes = sizeof(double) * (size_t)per * batch;
-  OCS_TRY(g->d_stage.ensure(bytes));
-  OCS_TRY(dst.ensure(bytes));
-  HIP_TRY(hipMemcpyAsync(g->d_stage.p, host, bytes, hipMemcpyHostToDevice, g->stream));
-  LAUNCH_TRY(launch_to_batch_minor(g->d_stage.d(), dst.d(), per, batch, g->stream));
-  return OCS_OK;
-}
-static int stage_out(ocs_integrator_s* g, const DevBuf& src, double* host, int per, int batch) {
-  const size_t bytes = sizeof(double) * (size_t)per * batch;
-  OCS_TRY(g->d_stage.ensure(bytes));
-  LAUNCH_TRY(launch_to_traj_major(src.d(), g->d_stage.d(), per, batch, g->stream));
-  HIP_TRY(hipMemcpyAsync(host, g->d_stage.p, bytes, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));  // d_stage is reused by the next stage_* call
-  return OCS_OK;
-}
-
 int ocs_compute_states(ocs_integrator g, ocs_problem p, int batch, const double* x0, const double* u,
                        double* x, double* J) {
   OCS_TRACE("ocs_compute_states");
@@ -493,15 +419,15 @@ int ocs_compute_states(ocs_integrator g, ocs_problem p, int batch, const double*
   OCS_TRY(upload_grid(g));
   const int nAug = p->nS + 1, nC = p->nC, N = g->N;
   HIP_TRY(hipStreamSynchronize(g->stream));
-  OCS_TRY(stage_in(g, x0, g->d_x0, p->nS, batch));
+  OCS_TRY(stage_in(g->d_stage, g->d_x0, x0, p->nS, batch, g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
-  OCS_TRY(stage_in(g, u, g->d_u, nC * (2 * N + 1), batch));
+  OCS_TRY(stage_in(g->d_stage, g->d_u, u, nC * (2 * N + 1), batch, g->stream));
   OCS_TRY(g->d_x.ensure(sizeof(double) * (size_t)nAug * (N + 1) * batch));
   OCS_TRY(g->d_J.ensure(sizeof(double) * batch));
   OCS_TRY(ocs_compute_states_dev(g, p, batch, g->d_x0.d(), g->d_u.d(), g->d_x.d(), g->d_J.d(), g->stream));
   HIP_TRY(hipMemcpyAsync(J, g->d_J.p, sizeof(double) * batch, hipMemcpyDeviceToHost, g->stream));
   if (x) {
-    OCS_TRY(stage_out(g, g->d_x, x, nAug * (N + 1), batch));
+    OCS_TRY(stage_out(g->d_stage, g->d_x.d(), x, nAug * (N + 1), batch, g->stream));
   } else {
     HIP_TRY(hipStreamSynchronize(g->stream));
   }
@@ -538,17 +464,17 @@ int ocs_compute_adjoints(ocs_integrator g, ocs_problem p, int batch, const doubl
     return fail(OCS_ERR_ORDER, "compute_adjoints needs compute_states first on the same handle/problem/batch");
   const int nAug = p->nS + 1, nC = p->nC, N = g->N;
   HIP_TRY(hipStreamSynchronize(g->stream));
-  OCS_TRY(stage_in(g, u, g->d_u, nC * (2 * N + 1), batch));
+  OCS_TRY(stage_in(g->d_stage, g->d_u, u, nC * (2 * N + 1), batch, g->stream));
   if (lamT) {
     HIP_TRY(hipStreamSynchronize(g->stream));
-    OCS_TRY(stage_in(g, lamT, g->d_lamT, nAug, batch));
+    OCS_TRY(stage_in(g->d_stage, g->d_lamT, lamT, nAug, batch, g->stream));
   }
   OCS_TRY(g->d_lam.ensure(sizeof(double) * (size_t)nAug * (N + 1) * batch));
   if (dJdu) OCS_TRY(g->d_dJdu.ensure(sizeof(double) * (size_t)nC * (2 * N + 1) * batch));
   OCS_TRY(ocs_compute_adjoints_dev(g, p, batch, g->d_u.d(), lamT ? g->d_lamT.d() : nullptr, g->d_lam.d(),
                                    dJdu ? g->d_dJdu.d() : nullptr, g->stream));
-  OCS_TRY(stage_out(g, g->d_lam, lam, nAug * (N + 1), batch));
-  if (dJdu) OCS_TRY(stage_out(g, g->d_dJdu, dJdu, nC * (2 * N + 1), batch));
+  OCS_TRY(stage_out(g->d_stage, g->d_lam.d(), lam, nAug * (N + 1), batch, g->stream));
+  if (dJdu) OCS_TRY(stage_out(g->d_stage, g->d_dJdu.d(), dJdu, nC * (2 * N + 1), batch, g->stream));
   return OCS_OK;
 }
 

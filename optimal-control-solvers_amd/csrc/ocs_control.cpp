@@ -4,8 +4,10 @@
 // constructors do; all per-trajectory arithmetic runs in the kernels.
 #include "ocs_trace.hpp"
 #include "ocs_handles.hpp"
+#include "ocs_matlab.hpp"
 
 #include <algorithm>
+#include <memory>
 
 using namespace ocs;
 
@@ -25,34 +27,12 @@ struct ocs_control_s {
   int device = -1;   // HIP device that owns the handle's memory (set at the first upload)
   hipStream_t stream = nullptr;
   DevBuf d_v, d_u, d_dJdu, d_dJdv, d_stage, d_x0, d_J, d_idx;
+  ~ocs_control_s() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 // ---- host helpers (MATLAB semantics) -------------------------------------------------------
-// linspace(d1, d2, n):  d1 + (0:n1).*(d2-d1)./n1 with the end points pinned
-static void matlab_linspace(double a, double b, int n, double* out) {
-  if (n <= 0) return;
-  if (n == 1) {
-    out[0] = b;
-    return;
-  }
-  const int n1 = n - 1;
-  for (int k = 0; k <= n1; ++k) out[k] = a + ((double)k * (b - a)) / (double)n1;
-  out[0] = a;
-  out[n1] = b;
-}
-static int interval_of(int n, const double* x, double q) {
-  if (q <= x[0]) return 0;
-  if (q >= x[n - 1]) return n - 2;
-  int lo = 0, hi = n - 1;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (x[mid] <= q)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
 // griddedInterpolant(x, v, 'linear', 'nearest')(q)   (PWLinearControl.m:35)
 static double tent_eval(int n, const double* x, const double* v, double q) {
   if (q < x[0]) return v[0];
@@ -78,8 +58,8 @@ static void pchip_slopes(int n, const double* x, const double* y, double* d) {
   }
   for (int k = 0; k < n - 2; ++k) {
     if (sgn(del[k]) * sgn(del[k + 1]) > 0) {
-      const double hs = h[k] + h[k + 1];
-      const double w1 = (h[k] + hs) / (3 * hs), w2 = (hs + h[k + 1]) / (3 * hs);
+      double w1, w2;
+      pchip_weight_pair(h[k], h[k + 1], &w1, &w2);
       const double a0 = std::fabs(del[k]), a1 = std::fabs(del[k + 1]);
       const double dmax = std::max(a0, a1), dmin = std::min(a0, a1);
       d[k + 1] = dmin / (w1 * (del[k] / dmax) + w2 * (del[k + 1] / dmax));
@@ -211,25 +191,6 @@ static int upload_control(ocs_control_s* c) {
   return OCS_OK;
 }
 
-// host staging on the control's own stream
-static int cstage_in(ocs_control_s* c, const double* host, DevBuf& dst, int per, int batch) {
-  const size_t bytes = sizeof(double) * (size_t)per * batch;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  OCS_TRY(c->d_stage.ensure(bytes));
-  OCS_TRY(dst.ensure(bytes));
-  HIP_TRY(hipMemcpyAsync(c->d_stage.p, host, bytes, hipMemcpyHostToDevice, c->stream));
-  LAUNCH_TRY(launch_to_batch_minor(c->d_stage.d(), dst.d(), per, batch, c->stream));
-  return OCS_OK;
-}
-static int cstage_out(ocs_control_s* c, const double* src, double* host, int per, int batch) {
-  const size_t bytes = sizeof(double) * (size_t)per * batch;
-  OCS_TRY(c->d_stage.ensure(bytes));
-  LAUNCH_TRY(launch_to_traj_major(src, c->d_stage.d(), per, batch, c->stream));
-  HIP_TRY(hipMemcpyAsync(host, c->d_stage.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return OCS_OK;
-}
-
 // 'nearest' / 'next' of griddedInterpolant: the index of the sample a query takes (-1: NaN).  Shared with ocs_interp_dev.
 namespace ocs {
 int interp_sample_index(int method, int n, const double* x, double q) {
@@ -256,7 +217,8 @@ int ocs_control_create(ocs_control* out, int kind, const double* t, int nt, int 
   if (nt < 2 || nBasis < 1 || nControls < 1) return fail(OCS_ERR_SHAPE, "need nt >= 2, nBasis >= 1, nControls >= 1");
   if (kind == OCS_CONTROL_PWLINEAR && nBasis < 2) return fail(OCS_ERR_SHAPE, "PWLinearControl needs >= 2 control points");
   if (kind < OCS_CONTROL_PWLINEAR || kind > OCS_CONTROL_CHEBYSHEV) return fail(OCS_ERR_UNSUPPORTED, "unknown control kind %d", kind);
-  ocs_control_s* c = new ocs_control_s();
+  std::unique_ptr<ocs_control_s> owner(new ocs_control_s());
+  ocs_control_s* c = owner.get();
   c->kind = kind;
   c->nBasis = nBasis;
   c->nC = nControls;
@@ -291,17 +253,12 @@ int ocs_control_create(ocs_control* out, int kind, const double* t, int nt, int 
       for (int i = 2; i < nBasis; ++i) Bm(i, j) = 2 * tT * Bm(i - 1, j) - Bm(i - 2, j);  // :28-30
     }
   }
-  *out = c;
+  *out = owner.release();
   return OCS_OK;
 }
 
 int ocs_control_destroy(ocs_control c) {
-  if (!c) return OCS_OK;
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  DevBuf* bufs[] = {&c->d_colptr, &c->d_row, &c->d_cval, &c->d_rowptr, &c->d_col, &c->d_rval, &c->d_BT, &c->d_BT16, &c->d_CT, &c->d_v,
-                    &c->d_u, &c->d_dJdu, &c->d_dJdv, &c->d_stage, &c->d_x0, &c->d_J, &c->d_idx};
-  for (DevBuf* b : bufs) b->release();
-  delete c;
+  delete c;   // (~ocs_control_s: the stream, then the buffers)
   return OCS_OK;
 }
 int ocs_control_dims(ocs_control c, int* nBasis, int* nControls, int* nt) {
@@ -351,20 +308,22 @@ int ocs_control_compute_u(ocs_control c, int batch, const double* v, double* u) 
   if (!c || !v || !u || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
   OCS_TRY(upload_control(c));
   const int nV = c->nC * c->nBasis, nU = c->nC * c->nT;
-  OCS_TRY(cstage_in(c, v, c->d_v, nV, batch));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (the stage buffer may still be in use)
+  OCS_TRY(stage_in(c->d_stage, c->d_v, v, nV, batch, c->stream));
   OCS_TRY(c->d_u.ensure(sizeof(double) * (size_t)nU * batch));
   OCS_TRY(ocs_control_compute_u_dev(c, batch, c->d_v.d(), c->d_u.d(), c->stream));
-  OCS_TRY(cstage_out(c, c->d_u.d(), u, nU, batch));
+  OCS_TRY(stage_out(c->d_stage, c->d_u.d(), u, nU, batch, c->stream));
   return OCS_OK;
 }
 int ocs_control_compute_dJdv(ocs_control c, int batch, const double* dJdu, double* dJdv) {
   if (!c || !dJdu || !dJdv || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
   OCS_TRY(upload_control(c));
   const int nV = c->nC * c->nBasis, nU = c->nC * c->nT;
-  OCS_TRY(cstage_in(c, dJdu, c->d_dJdu, nU, batch));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (the stage buffer may still be in use)
+  OCS_TRY(stage_in(c->d_stage, c->d_dJdu, dJdu, nU, batch, c->stream));
   OCS_TRY(c->d_dJdv.ensure(sizeof(double) * (size_t)nV * batch));
   OCS_TRY(ocs_control_compute_dJdv_dev(c, batch, c->d_dJdu.d(), c->d_dJdv.d(), c->stream));
-  OCS_TRY(cstage_out(c, c->d_dJdv.d(), dJdv, nV, batch));
+  OCS_TRY(stage_out(c->d_stage, c->d_dJdv.d(), dJdv, nV, batch, c->stream));
   return OCS_OK;
 }
 
@@ -601,15 +560,17 @@ int ocs_nlp_objective(ocs_integrator g, ocs_problem p, ocs_control c, int batch,
   if (nFree > 0) {  // reserve the index + lam0 scratch before any pointer into it is formed
     OCS_TRY(c->d_idx.ensure(((sizeof(int) * nFree + 7) / 8) * 8 + sizeof(double) * (size_t)(p->nS + 1) * batch));
   }
-  OCS_TRY(cstage_in(c, v, c->d_v, nV, batch));
-  OCS_TRY(cstage_in(c, x0, c->d_x0, p->nS, batch));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (the stage buffer may still be in use)
+  OCS_TRY(stage_in(c->d_stage, c->d_v, v, nV, batch, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (the stage buffer may still be in use)
+  OCS_TRY(stage_in(c->d_stage, c->d_x0, x0, p->nS, batch, c->stream));
   OCS_TRY(c->d_J.ensure(sizeof(double) * batch));
   OCS_TRY(c->d_dJdv.ensure(sizeof(double) * (size_t)nV * batch));
   OCS_TRY(ocs_nlp_objective_dev(g, p, c, batch, c->d_x0.d(), c->d_v.d(), nFree, FreeInitStates, c->d_J.d(),
                                 c->d_dJdv.d(), c->stream));
   HIP_TRY(hipMemcpyAsync(J, c->d_J.p, sizeof(double) * batch, hipMemcpyDeviceToHost, c->stream));
-  OCS_TRY(cstage_out(c, c->d_dJdv.d(), dJdv, nV, batch));
-  if (nFree > 0) OCS_TRY(cstage_out(c, c->d_x0.d(), x0, p->nS, batch));
+  OCS_TRY(stage_out(c->d_stage, c->d_dJdv.d(), dJdv, nV, batch, c->stream));
+  if (nFree > 0) OCS_TRY(stage_out(c->d_stage, c->d_x0.d(), x0, p->nS, batch, c->stream));
   g->traj_status.assign(batch, 0);
   int rc = OCS_OK;
   for (int b = 0; b < batch; ++b)

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <string>
 #include "ocs_handles.hpp"
+#include "ocs_matlab.hpp"
 
 #include <algorithm>
 
@@ -41,35 +42,14 @@ struct ocs_fbs_state {
   DevBuf nact_slots;                // device: the same counters
   // work arrays
   DevBuf xaug, xmid, lam, lmid, ugrid, uerr, uint_, J, usel, status, maxchange, nactive, x0, stage, metric, anyvalid, dump;
+  ~ocs_fbs_state() {
+    if (lq_event) (void)hipEventDestroy(lq_event);
+    for (hipEvent_t e : wevents) (void)hipEventDestroy(e);
+    if (h_nact) (void)hipHostFree(h_nact);
+  }
 };
 
-void ocs_fbs_state_free(ocs_fbs_state* s) {
-  if (!s) return;
-  s->QSE.release();
-  DevBuf* bufs[] = {&s->TN, &s->HN, &s->W1, &s->W2, &s->TM, &s->IH, &s->PR, &s->KE, &s->SE, &s->TE, &s->TUE, &s->KI, &s->SI,
-                    &s->TI, &s->TUI, &s->xaug, &s->xmid, &s->lam, &s->lmid, &s->ugrid, &s->uerr, &s->uint_, &s->J,
-                    &s->usel, &s->status, &s->maxchange, &s->nactive, &s->x0, &s->stage, &s->metric, &s->anyvalid, &s->dump};
-  for (DevBuf* b : bufs) b->release();
-  s->nact_slots.release();
-  s->lq_TC.release();
-  s->lq_REC.release();
-  if (s->lq_event) (void)hipEventDestroy(s->lq_event);
-  for (hipEvent_t e : s->wevents) (void)hipEventDestroy(e);
-  if (s->h_nact) (void)hipHostFree(s->h_nact);
-  delete s;
-}
-
-static void matlab_linspace(double a, double b, int n, std::vector<double>& out) {
-  out.resize(n);
-  if (n == 1) {
-    out[0] = b;
-    return;
-  }
-  const int n1 = n - 1;
-  for (int k = 0; k <= n1; ++k) out[k] = a + ((double)k * (b - a)) / (double)n1;
-  out[0] = a;
-  out[n1] = b;
-}
+void ocs_fbs_state_free(ocs_fbs_state* s) { delete s; }
 
 static int upload(DevBuf& d, const void* src, size_t bytes) {
   OCS_TRY(d.ensure(bytes ? bytes : 8));
@@ -82,15 +62,11 @@ static int ensure_tables(ocs_integrator_s* g) {
   ocs_fbs_state* f = g->fbs;
   if (f->tables) return OCS_OK;
   const int N = g->N, n = N + 1;
-  std::vector<double> tn(n), tm(N), w1(n, 0.0), w2(n, 0.0);
+  std::vector<double> tn(n), tm(N), w1(n), w2(n);
   for (int i = 0; i < n; ++i) tn[i] = g->t[2 * (size_t)i];
   for (int i = 0; i < N; ++i) tm[i] = g->t[2 * (size_t)i + 1];
   const std::vector<double>& h = g->h;
-  for (int k = 1; k + 1 < n; ++k) {  // pchip interior weights (MATLAB pchipslopes)
-    const double hs = h[k - 1] + h[k];
-    w1[k] = (h[k - 1] + hs) / (3 * hs);
-    w2[k] = (hs + h[k]) / (3 * hs);
-  }
+  pchip_weights(n, h.data(), w1.data(), w2.data());
   OCS_TRY(upload(f->TN, tn.data(), sizeof(double) * n));
   OCS_TRY(upload(f->HN, h.data(), sizeof(double) * N));
   OCS_TRY(upload(f->W1, w1.data(), sizeof(double) * n));
@@ -132,27 +108,13 @@ static FbsTables tabs(const ocs_integrator_s* g) {
 static int build_points(ocs_integrator_s* g, int nq, DevBuf& K, DevBuf& S, DevBuf& T, bool* on_nodes = nullptr,
                         DevBuf* QS = nullptr) {
   const int n = g->N + 1;
-  std::vector<double> q, tn(n), s(nq);
+  std::vector<double> q(nq), tn(n), s(nq);
   std::vector<int> k(nq);
   for (int i = 0; i < n; ++i) tn[i] = g->t[2 * (size_t)i];
-  matlab_linspace(tn[0], tn[n - 1], nq, q);  // fb_sweep.m:69-70
+  matlab_linspace(tn[0], tn[n - 1], nq, q.data());  // fb_sweep.m:69-70
   for (int j = 0; j < nq; ++j) {
-    int lo = 0, hi = n - 1;
-    if (q[j] <= tn[0])
-      lo = 0;
-    else if (q[j] >= tn[n - 1])
-      lo = n - 2;
-    else {
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if (tn[mid] <= q[j])
-          lo = mid;
-        else
-          hi = mid;
-      }
-    }
-    k[j] = lo;
-    s[j] = q[j] - tn[lo];
+    k[j] = interval_of(n, tn.data(), q[j]);
+    s[j] = q[j] - tn[k[j]];
   }
   if (on_nodes) {
     // "the same" up to a few units in the last place of the horizon: a tspan from another linspace than MATLAB's (numpy's
@@ -175,6 +137,17 @@ static int build_points(ocs_integrator_s* g, int nq, DevBuf& K, DevBuf& S, DevBu
   return OCS_OK;
 }
 
+// soln.x has the nS state rows: xaug [npts][nS + 1][B] staged out whole, the running-objective row dropped on the host
+static int stage_out_states(DevBuf& stage, const double* xaug, double* x, int nS, int npts, int batch, hipStream_t s) {
+  const int nAug = nS + 1;
+  std::vector<double> tmp((size_t)npts * nAug * batch);
+  OCS_TRY(stage_out(stage, xaug, tmp.data(), npts * nAug, batch, s));
+  for (size_t b = 0; b < (size_t)batch; ++b)
+    for (int i = 0; i < npts; ++i)
+      for (int k = 0; k < nS; ++k) x[(b * npts + i) * nS + k] = tmp[(b * npts + i) * nAug + k];
+  return OCS_OK;
+}
+
 extern "C" {
 
 // vectorInterpolant(x, v, method)(tq) for a batch of sample sets on the device (functions/vectorInterpolant.m:1-12;
@@ -192,32 +165,16 @@ int ocs_interp_dev(int method, int nComp, int n, const double* x, const double* 
     if (!(x[i + 1] > x[i])) return fail(OCS_ERR_INVALID, "sample points must increase strictly");
   if (nq == 0) return OCS_OK;
   hipStream_t s = (hipStream_t)stream;
-  std::vector<double> h(n - 1), ih(n - 1), w1(n, 0.0), w2(n, 0.0), sq(nq);
+  std::vector<double> h(n - 1), ih(n - 1), w1(n), w2(n), sq(nq);
   std::vector<int> kq(nq);
   for (int i = 0; i + 1 < n; ++i) {
     h[i] = x[i + 1] - x[i];
     ih[i] = 1.0 / h[i];
   }
-  for (int k = 1; k + 1 < n; ++k) {  // pchip interior weights (MATLAB pchipslopes)
-    const double hs = h[k - 1] + h[k];
-    w1[k] = (h[k - 1] + hs) / (3 * hs);
-    w2[k] = (hs + h[k]) / (3 * hs);
-  }
+  pchip_weights(n, h.data(), w1.data(), w2.data());
   for (int j = 0; j < nq; ++j) {
     const double q = tq[j];
-    int lo = 0, hi = n - 1;
-    if (q <= x[0])
-      lo = 0;
-    else if (q >= x[n - 1])
-      lo = n - 2;
-    else
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if (x[mid] <= q)
-          lo = mid;
-        else
-          hi = mid;
-      }
+    int lo = interval_of(n, x, q);
     if (method == OCS_INTERP_PREVIOUS) lo = q < x[0] ? -1 : (q >= x[n - 1] ? n - 1 : lo);
     if (method == OCS_INTERP_NEAREST || method == OCS_INTERP_NEXT) lo = interp_sample_index(method, n, x, q);
     kq[j] = lo;
@@ -260,20 +217,32 @@ int ocs_interp_dev(int method, int nComp, int n, const double* x, const double* 
     memcpy(hp + oQS, qs.data(), sizeof(int) * n);
     memcpy(hp + oQI, qi.data(), sizeof(int) * nq);
   }
+  // NOT an owning DevBuf: a thread-local one would call hipFree at thread exit (the workers of ocs_multi_*) or at process exit
+  // (the main thread), possibly after the HIP runtime has shut down.  The holder has no destructor; the memory is never freed.
   struct Scratch {
-    DevBuf buf;
+    void* p = nullptr;
+    size_t cap = 0;
     int device = -1;
   };
   static thread_local Scratch scratch;
   int devnow = 0;
   HIP_TRY(hipGetDevice(&devnow));
   if (scratch.device != devnow) {   // (a buffer of another device: dropped, not freed from here)
-    scratch.buf = DevBuf();
+    scratch.p = nullptr;
+    scratch.cap = 0;
     scratch.device = devnow;
   }
-  OCS_TRY(scratch.buf.ensure(sizeof(double) * nd));
-  HIP_TRY(hipMemcpyAsync(scratch.buf.p, hp, sizeof(double) * nd, hipMemcpyHostToDevice, s));
-  double* dp = scratch.buf.d();
+  {
+    DevBuf grow;   // owns the scratch while it grows, and hands it back
+    grow.p = scratch.p;
+    grow.cap = scratch.cap;
+    const int rc = grow.ensure(sizeof(double) * nd);
+    scratch.cap = grow.cap;
+    scratch.p = grow.detach();
+    OCS_TRY(rc);
+  }
+  HIP_TRY(hipMemcpyAsync(scratch.p, hp, sizeof(double) * nd, hipMemcpyHostToDevice, s));
+  double* dp = static_cast<double*>(scratch.p);
   const FbsTables tb{n, dp, dp + n, dp + 2 * (size_t)n, dp + 3 * (size_t)n, nullptr, dp + 4 * (size_t)n, nullptr};
   // ('nearest' and 'next' pick a sample like 'previous' does: the kernel's sample-index mode)
   const int kmethod = (method == OCS_INTERP_NEAREST || method == OCS_INTERP_NEXT) ? OCS_INTERP_PREVIOUS : method;
@@ -432,24 +401,16 @@ int ocs_problem_ControlChar(ocs_problem p, int k, const double* t, const double*
   OCS_TRY(upload_problem(p));
   const int nS = p->nS, nC = p->nC;
   DevBuf dt, dx, dl, dout;
-  auto body = [&]() -> int {
-    OCS_TRY(dt.ensure(sizeof(double) * k));
-    OCS_TRY(dx.ensure(sizeof(double) * (size_t)nS * k));
-    OCS_TRY(dl.ensure(sizeof(double) * (size_t)nS * k));
-    OCS_TRY(dout.ensure(sizeof(double) * (size_t)nC * k));
-    HIP_TRY(hipMemcpy(dt.p, t, sizeof(double) * k, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dx.p, x, sizeof(double) * (size_t)nS * k, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dl.p, lam, sizeof(double) * (size_t)nS * k, hipMemcpyHostToDevice));
-    LAUNCH_TRY(launch_eval(describe(p), 3, k, dt.d(), dx.d(), nullptr, dl.d(), dout.d(), nullptr));
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * (size_t)nC * k, hipMemcpyDeviceToHost));
-    return OCS_OK;
-  };
-  const int rc = body();
-  dt.release();
-  dx.release();
-  dl.release();
-  dout.release();
-  return rc;
+  OCS_TRY(dt.ensure(sizeof(double) * k));
+  OCS_TRY(dx.ensure(sizeof(double) * (size_t)nS * k));
+  OCS_TRY(dl.ensure(sizeof(double) * (size_t)nS * k));
+  OCS_TRY(dout.ensure(sizeof(double) * (size_t)nC * k));
+  HIP_TRY(hipMemcpy(dt.p, t, sizeof(double) * k, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dx.p, x, sizeof(double) * (size_t)nS * k, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dl.p, lam, sizeof(double) * (size_t)nS * k, hipMemcpyHostToDevice));
+  LAUNCH_TRY(launch_eval(describe(p), 3, k, dt.d(), dx.d(), nullptr, dl.d(), dout.d(), nullptr));
+  HIP_TRY(hipMemcpy(out, dout.p, sizeof(double) * (size_t)nC * k, hipMemcpyDeviceToHost));
+  return OCS_OK;
 }
 
 // [x, lam] = compute_x_lam(prob, x0, tspan, u, ...) / [x, lam, J] = compute_x_lam_J(...) on the grid.
@@ -593,9 +554,10 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
     if (lqmc) return launch_sweep_forward_lq(lqd, lqg, batch, x0, f->ugrid.d(), xaug, J, fo.frozen, fo.gate, s);
     return launch_forward(pd, gd, batch, x0, f->ugrid.d(), xaug, J, fo, s);
   };
-  auto costate_pass = [&](const double* xmid, const double* PR, const int* gate) -> int {
+  // (PR: read only where the costate kernel forms the midpoints itself, xmid == NULL)
+  auto costate_pass = [&](const double* xmid, const int* gate) -> int {
     if (lqmc) return xmid ? launch_sweep_costate_lq(lqd, lqg, batch, xaug, nAug, xmid, status, lam, gate, s) : -1;
-    return launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, PR, gate);
+    return launch_costate(pd, gd, batch, xaug, nAug, xmid, f->ugrid.d(), status, f->dump.d(), lam, s, tb.PR, gate);
   };
   // every sweep with the control update folded into the state pass (see below): the grid samples of u are never formed
   // (not with a damped update: that needs the samples of the control it damps)
@@ -614,6 +576,51 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
     if (!fusedup) LAUNCH_TRY(launch_fill_rows(nE, nC, batch, p->d_lb.d(), f->uerr.d(), s));
   }
   const int* usel = (const int*)f->usel.p;  // selects the old / new buffer of the ERROR-POINT samples only
+  // ---- the kernels of one sweep (all but the folded sweep of path 4) ---------------------------------------------------
+  // uNew = sweep(u): compute_x_lam (:95), uNew = ControlChar(t, x(t), lam(t)) (:96), check_convergence(uNew, u) (:81, :99-115)
+  // and u = uNew (:85).  What differs between the callers:
+  //   gate  the count of instances still active after the sweep before, which every kernel looks at first (NULL: no look)
+  //   slot  where k_fbs_advance counts the instances still active after this sweep (path 1 has ONE counter, f->nactive, which
+  //         is zeroed here for every sweep, where it always was: between the midpoint and the costate kernel; the slots of the
+  //         sweeps enqueued ahead are zeroed together before the first)
+  //   ownx  the costate and control kernels form the pchip midpoints of x themselves (no midpoint kernel, no xmid array)
+  auto control_grid = [&](const double* xmid, double* metric, const int* gate) -> int {
+    return launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, metric, metric ? opt->uRelTol : 0.0,
+                               metric ? opt->uAbsTol : 0.0, s, gate, om);
+  };
+  auto sweep_kernels = [&](int sweep, const int* gate, int* slot, bool ownx) -> int {
+    // instances that converged in an earlier sweep are integrated along but store nothing: their x, lam, J stay those of
+    // the sweep they converged in (final_sweep(u), :82)
+    FwdOpts fo;
+    fo.frozen = status;
+    fo.dump = f->dump.d();
+    fo.no_cost_row = opt->cost_row == 0;  // soln holds x, lam, u and the scalar J (fb_sweep.m:117-125)
+    fo.gate = gate;
+    LAUNCH_TRY(state_pass(fo));
+    const double* xmid = ownx ? nullptr : f->xmid.d();
+    if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s, gate));
+    if (slot == (int*)f->nactive.p) HIP_TRY(hipMemsetAsync(slot, 0, sizeof(int), s));
+    LAUNCH_TRY(costate_pass(xmid, gate));
+    if (fusedup) {
+      // error points on the nodes: uNew on the grid, in place, with the weighted change at the nodes (:107) folded in.  A
+      // just-converged instance takes uNew as well, but it is frozen from now on: its x, lam, J are the ones computed above
+      // from the old control, which is what final_sweep(u) returns (:82).
+      LAUNCH_TRY(control_grid(xmid, f->metric.d(), gate));
+    } else if (cps) {   // error points off the nodes: uNew there with check_convergence folded in
+      LAUNCH_TRY(launch_control_pts_sorted(pd, tb, nE, (const int*)f->QSE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
+                                           f->uerr.d(), f->metric.d(), opt->uRelTol, opt->uAbsTol, s, om, gate));
+    } else {
+      LAUNCH_TRY(launch_control_pts(pd, tb, nE, (const int*)f->KE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
+                                    f->uerr.d(), usel, (long long)uerrN, f->metric.d(), (int*)f->anyvalid.p, opt->uRelTol,
+                                    opt->uAbsTol, s, om, gate));
+    }
+    LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status, mc, slot,
+                                  s, gate));
+    // ... then u = uNew on the grid, only for the instances that continue (status is the one k_fbs_advance just wrote): a
+    // converged instance keeps its OLD control, which is what final_sweep(u) integrates (:85 / :82)
+    if (!fusedup) LAUNCH_TRY(control_grid(xmid, nullptr, gate));
+    return OCS_OK;
+  };
   int nactive = batch;
   f->last_path = 1;
   // ---- fused update, one stream, sweeps enqueued one ahead --------------------------------------------------------
@@ -621,13 +628,12 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   // enqueuing sweep k+1 left the GPU idle for ~25 us per sweep.  Here sweep k+1 is enqueued first and its kernels
   // start with a look at sweep k's device counter: if no instance was left, they return at once (a sweep over
   // converged instances would change nothing anyway -- they are frozen -- but would cost its full time).
-  bool spec_done = false;
   // (every state pass of the sweep takes the gate -- the wave-specialised kernels, split passes, the lane kernel of any
   //  plugin -- so the loop is the same for every problem: what differs is whether the pchip midpoints of x are a kernel
   //  of their own)
   // ... and the same for error points OFF the grid nodes (the reference's default of 1001 points on any grid but N = 1000, a given
-  // u0): the kernels of the kernel-by-kernel sequence below, gated and enqueued ahead (path 5).  That sequence waited for the
-  // host once per sweep: 485 against ~250 us per sweep at 500 steps.
+  // u0): the same kernels, gated and enqueued ahead (path 5).  Path 1 below waits for the host once per sweep: 485 against
+  // ~250 us per sweep at 500 steps.
   const bool ahead1 = !fusedup && fuo == 0;
   if (fusedup || ahead1) {
     const int nsw = opt->nSWEEPS;
@@ -672,34 +678,7 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
         LAUNCH_TRY(launch_costate_met(pd, gd, batch, xaug, nAug, tb.PR, p->d_lb.d(), p->d_ub.d(), opt->uRelTol,
                                       opt->uAbsTol, sweep, status, mc, dslots + (sweep - 1), lam, s, gate));
       } else {
-        FwdOpts fo;
-        fo.frozen = status;
-        fo.dump = f->dump.d();
-        fo.no_cost_row = opt->cost_row == 0;
-        fo.gate = gate;
-        LAUNCH_TRY(state_pass(fo));
-        const double* xmid = ownx ? nullptr : f->xmid.d();
-        if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s, gate));
-        LAUNCH_TRY(costate_pass(xmid, tb.PR, gate));
-        if (!fusedup) {   // error points off the nodes: uNew there with check_convergence (:96, :99-115), then u = uNew on the grid
-          if (cps)
-            LAUNCH_TRY(launch_control_pts_sorted(pd, tb, nE, (const int*)f->QSE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
-                                                 f->uerr.d(), f->metric.d(), opt->uRelTol, opt->uAbsTol, s, om, gate));
-          else
-            LAUNCH_TRY(launch_control_pts(pd, tb, nE, (const int*)f->KE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
-                                          f->uerr.d(), usel, (long long)uerrN, f->metric.d(), (int*)f->anyvalid.p, opt->uRelTol,
-                                          opt->uAbsTol, s, om, gate));
-          LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
-                                        mc, dslots + (sweep - 1), s, gate));
-          // (only the instances that continue take uNew: status is the one k_fbs_advance just wrote, :85 / :82)
-          LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, nullptr, 0.0, 0.0, s, gate,
-                                         om));
-        } else {
-          LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, f->metric.d(),
-                                         opt->uRelTol, opt->uAbsTol, s, gate, om));
-          LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
-                                        mc, dslots + (sweep - 1), s, gate));
-        }
+        OCS_TRY(sweep_kernels(sweep, gate, dslots + (sweep - 1), ownx));
       }
       // the sweep's count of active instances to the host, and the event the host waits on
       HIP_TRY(hipMemcpyAsync(f->h_nact + (sweep - 1), dslots + (sweep - 1), sizeof(int), hipMemcpyDeviceToHost, s));
@@ -713,54 +692,13 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
       nactive = f->h_nact[sweep - 1];
       if (nactive == 0) break;  // the sweeps already enqueued find their gates closed
     }
-    spec_done = true;
-  }
-  for (int sweep = 1; !spec_done && sweep <= opt->nSWEEPS && nactive > 0; ++sweep) {  // :79
-    // uNew = sweep(u): compute_x_lam (:95) ...
-    // instances that converged in an earlier sweep are integrated along but store nothing: their x, lam, J stay
-    // those of the sweep they converged in (final_sweep(u), :82)
-    FwdOpts fo;
-    fo.frozen = status;
-    fo.dump = f->dump.d();
-    fo.no_cost_row = opt->cost_row == 0;  // soln holds x, lam, u and the scalar J (fb_sweep.m:117-125)
-    LAUNCH_TRY(state_pass(fo));
-    // pchip midpoints of x: inside the costate and control kernels where the wave-specialised costate kernel applies
-    const bool ownx = !lqmc && fusedup && fuo == 0 && costate_forms_midpoints(pd, N, batch);
-    const double* xmid = ownx ? nullptr : f->xmid.d();
-    if (!ownx) LAUNCH_TRY(launch_pchip_mid(tb, nS, nAug, batch, xaug, f->xmid.d(), s));
-    HIP_TRY(hipMemsetAsync(f->nactive.p, 0, sizeof(int), s));
-    if (fusedup) {
-      // costate (:95); uNew = ControlChar(t, x(t), lam(t)) on the grid, in place (:96, :85), with the weighted change at
-      // the nodes (:107) folded in.  A just-converged instance takes uNew as well, but it is frozen from now on: its
-      // x, lam, J are the ones computed above from the old control, which is what final_sweep(u) returns (:82).
-      LAUNCH_TRY(costate_pass(xmid, tb.PR, nullptr));
-      LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, xmid, lam, f->ugrid.d(), status, f->metric.d(),
-                                     opt->uRelTol, opt->uAbsTol, s, nullptr, om));
-      LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p, (int*)f->usel.p, status,
-                                    mc, (int*)f->nactive.p, s));
+  } else {
+    // ---- path 1: the same kernels without a gate, the host waits for the count of every sweep -----------------------
+    for (int sweep = 1; sweep <= opt->nSWEEPS && nactive > 0; ++sweep) {  // :79
+      OCS_TRY(sweep_kernels(sweep, nullptr, (int*)f->nactive.p, false));
       HIP_TRY(hipMemcpyAsync(&nactive, f->nactive.p, sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
-      continue;
     }
-    LAUNCH_TRY(costate_pass(f->xmid.d(), nullptr, nullptr));
-    // ... uNew = ControlChar(t, x(t), lam(t)) (:96) on the error points, with check_convergence(uNew, u)
-    // (:81, :99-115) folded in
-    if (cps)
-      LAUNCH_TRY(launch_control_pts_sorted(pd, tb, nE, (const int*)f->QSE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
-                                           f->uerr.d(), f->metric.d(), opt->uRelTol, opt->uAbsTol, s, om));
-    else
-      LAUNCH_TRY(launch_control_pts(pd, tb, nE, (const int*)f->KE.p, f->SE.d(), f->TUE.d(), batch, xaug, nAug, lam,
-                                    f->uerr.d(), usel, (long long)uerrN, f->metric.d(),
-                                    (int*)f->anyvalid.p, opt->uRelTol, opt->uAbsTol, s, om));
-    LAUNCH_TRY(launch_fbs_advance(batch, sweep, nparts, f->metric.d(), (int*)f->anyvalid.p,
-                                  (int*)f->usel.p, status, mc, (int*)f->nactive.p, s));
-    // u = uNew (:85) on the integrator grid, only for the instances that continue: a converged instance
-    // keeps its OLD control, which is what final_sweep(u) integrates (:82)
-    // (lam's pchip midpoints are formed inside the kernel)
-    LAUNCH_TRY(launch_control_grid(pd, gd, tb, batch, xaug, nAug, f->xmid.d(), lam, f->ugrid.d(), status, nullptr, 0.0, 0.0,
-                                   s, nullptr, om));
-    HIP_TRY(hipMemcpyAsync(&nactive, f->nactive.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
   }
   // final_sweep(u) (:82, :117-125): x, lam, J of a converged instance already belong to its OLD control
   // (a frozen instance is re-integrated with the same u each later sweep, bit for bit); what is left is
@@ -789,61 +727,32 @@ int ocs_fb_sweep(ocs_integrator g, ocs_problem p, int batch, const double* x0, c
   const int nE = opt->nERROR_PTS, nI = opt->nINTERP_PTS;
   const size_t B = (size_t)batch;
   hipStream_t s = g->stream;
-  auto in = [&](const double* host, DevBuf& dst, int per) -> int {
-    const size_t bytes = sizeof(double) * (size_t)per * B;
-    HIP_TRY(hipStreamSynchronize(s));
-    OCS_TRY(f->stage.ensure(bytes));
-    OCS_TRY(dst.ensure(bytes));
-    HIP_TRY(hipMemcpyAsync(f->stage.p, host, bytes, hipMemcpyHostToDevice, s));
-    LAUNCH_TRY(launch_to_batch_minor(f->stage.d(), dst.d(), per, batch, s));
-    return OCS_OK;
-  };
-  auto out = [&](const double* src, double* host, int per) -> int {
-    const size_t bytes = sizeof(double) * (size_t)per * B;
-    OCS_TRY(f->stage.ensure(bytes));
-    LAUNCH_TRY(launch_to_traj_major(src, f->stage.d(), per, batch, s));
-    HIP_TRY(hipMemcpyAsync(host, f->stage.p, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return OCS_OK;
-  };
-  OCS_TRY(in(x0, f->x0, nS));
+  HIP_TRY(hipStreamSynchronize(s));   // (before every stage_in here: the stage buffer may still be in use)
+  OCS_TRY(stage_in(f->stage, f->x0, x0, nS, batch, s));
   DevBuf dug, due;
-  int rc = OCS_OK;
-  auto body = [&]() -> int {
-    if (u0grid) {
-      OCS_TRY(in(u0grid, dug, nC * nT));
-      OCS_TRY(in(u0err, due, nC * nE));
-    }
-    OCS_TRY(f->xaug.ensure(sizeof(double) * (size_t)(N + 1) * nAug * B));
-    OCS_TRY(f->lam.ensure(sizeof(double) * (size_t)(N + 1) * nS * B));
-    OCS_TRY(f->uint_.ensure(sizeof(double) * (size_t)nI * nC * B));
-    OCS_TRY(f->J.ensure(sizeof(double) * B));
-    OCS_TRY(f->status.ensure(sizeof(int) * B));
-    OCS_TRY(f->maxchange.ensure(sizeof(double) * (size_t)opt->nSWEEPS * B));
-    const int st = ocs_fb_sweep_dev(g, p, batch, f->x0.d(), opt, u0grid ? dug.d() : nullptr, u0grid ? due.d() : nullptr,
-                                    f->xaug.d(), f->lam.d(), f->uint_.d(), f->J.d(), (int*)f->status.p,
-                                    f->maxchange.d(), s);
-    if (st < 0) return st;
-    // drop the running-objective row: soln.x has the nS state rows
-    std::vector<double> tmp((size_t)(N + 1) * nAug * B);
-    OCS_TRY(out(f->xaug.d(), tmp.data(), (N + 1) * nAug));
-    for (size_t b = 0; b < B; ++b)
-      for (int i = 0; i <= N; ++i)
-        for (int k = 0; k < nS; ++k)
-          x[(b * (N + 1) + i) * nS + k] = tmp[(b * (N + 1) + i) * nAug + k];
-    OCS_TRY(out(f->lam.d(), lam, (N + 1) * nS));
-    OCS_TRY(out(f->uint_.d(), uInterp, nI * nC));
-    HIP_TRY(hipMemcpy(J, f->J.p, sizeof(double) * B, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sweeps, f->status.p, sizeof(int) * B, hipMemcpyDeviceToHost));
-    if (maxChange) {  // [nSWEEPS][B] on the device -> nSWEEPS x batch column-major on the host
-      OCS_TRY(out(f->maxchange.d(), maxChange, opt->nSWEEPS));
-    }
-    return st;
-  };
-  rc = body();
-  dug.release();
-  due.release();
-  return rc;
+  if (u0grid) {
+    HIP_TRY(hipStreamSynchronize(s));
+    OCS_TRY(stage_in(f->stage, dug, u0grid, nC * nT, batch, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    OCS_TRY(stage_in(f->stage, due, u0err, nC * nE, batch, s));
+  }
+  OCS_TRY(f->xaug.ensure(sizeof(double) * (size_t)(N + 1) * nAug * B));
+  OCS_TRY(f->lam.ensure(sizeof(double) * (size_t)(N + 1) * nS * B));
+  OCS_TRY(f->uint_.ensure(sizeof(double) * (size_t)nI * nC * B));
+  OCS_TRY(f->J.ensure(sizeof(double) * B));
+  OCS_TRY(f->status.ensure(sizeof(int) * B));
+  OCS_TRY(f->maxchange.ensure(sizeof(double) * (size_t)opt->nSWEEPS * B));
+  const int st = ocs_fb_sweep_dev(g, p, batch, f->x0.d(), opt, u0grid ? dug.d() : nullptr, u0grid ? due.d() : nullptr,
+                                  f->xaug.d(), f->lam.d(), f->uint_.d(), f->J.d(), (int*)f->status.p, f->maxchange.d(), s);
+  if (st < 0) return st;
+  OCS_TRY(stage_out_states(f->stage, f->xaug.d(), x, nS, N + 1, batch, s));
+  OCS_TRY(stage_out(f->stage, f->lam.d(), lam, (N + 1) * nS, batch, s));
+  OCS_TRY(stage_out(f->stage, f->uint_.d(), uInterp, nI * nC, batch, s));
+  HIP_TRY(hipMemcpy(J, f->J.p, sizeof(double) * B, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sweeps, f->status.p, sizeof(int) * B, hipMemcpyDeviceToHost));
+  // [nSWEEPS][B] on the device -> nSWEEPS x batch column-major on the host
+  if (maxChange) OCS_TRY(stage_out(f->stage, f->maxchange.d(), maxChange, opt->nSWEEPS, batch, s));
+  return st;
 }
 
 // host compute_x_lam(_J): x0 nS x batch, ugrid nC x (2N+1) x batch -> x nS x (N+1) x batch, lam same, J (or NULL)
@@ -858,38 +767,18 @@ int ocs_compute_x_lam(ocs_integrator g, ocs_problem p, int batch, const double* 
   const size_t B = (size_t)batch;
   hipStream_t s = g->stream;
   DevBuf dug;
-  auto body = [&]() -> int {
-    const size_t bx = sizeof(double) * (size_t)nS * B, bu = sizeof(double) * (size_t)nC * nT * B;
-    OCS_TRY(f->stage.ensure(std::max(bx, bu)));
-    OCS_TRY(f->x0.ensure(bx));
-    OCS_TRY(dug.ensure(bu));
-    HIP_TRY(hipMemcpy(f->stage.p, x0, bx, hipMemcpyHostToDevice));
-    LAUNCH_TRY(launch_to_batch_minor(f->stage.d(), f->x0.d(), nS, batch, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(f->stage.p, ugrid, bu, hipMemcpyHostToDevice));
-    LAUNCH_TRY(launch_to_batch_minor(f->stage.d(), dug.d(), nC * nT, batch, s));
-    OCS_TRY(f->xaug.ensure(sizeof(double) * (size_t)(N + 1) * nAug * B));
-    OCS_TRY(f->lam.ensure(sizeof(double) * (size_t)(N + 1) * nS * B));
-    OCS_TRY(f->J.ensure(sizeof(double) * B));
-    OCS_TRY(ocs_compute_x_lam_dev(g, p, batch, f->x0.d(), dug.d(), f->xaug.d(), f->lam.d(), f->J.d(), s));
-    std::vector<double> tmp((size_t)(N + 1) * nAug * B);
-    OCS_TRY(f->stage.ensure(sizeof(double) * tmp.size()));
-    LAUNCH_TRY(launch_to_traj_major(f->xaug.d(), f->stage.d(), (N + 1) * nAug, batch, s));
-    HIP_TRY(hipMemcpyAsync(tmp.data(), f->stage.p, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t b = 0; b < B; ++b)
-      for (int i = 0; i <= N; ++i)
-        for (int k = 0; k < nS; ++k)
-          x[(b * (N + 1) + i) * nS + k] = tmp[(b * (N + 1) + i) * nAug + k];
-    LAUNCH_TRY(launch_to_traj_major(f->lam.d(), f->stage.d(), (N + 1) * nS, batch, s));
-    HIP_TRY(hipMemcpyAsync(lam, f->stage.p, sizeof(double) * (size_t)(N + 1) * nS * B, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (J) HIP_TRY(hipMemcpy(J, f->J.p, sizeof(double) * B, hipMemcpyDeviceToHost));
-    return OCS_OK;
-  };
-  const int rc = body();
-  dug.release();
-  return rc;
+  HIP_TRY(hipStreamSynchronize(s));   // (before every stage_in here: the stage buffer may still be in use)
+  OCS_TRY(stage_in(f->stage, f->x0, x0, nS, batch, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  OCS_TRY(stage_in(f->stage, dug, ugrid, nC * nT, batch, s));
+  OCS_TRY(f->xaug.ensure(sizeof(double) * (size_t)(N + 1) * nAug * B));
+  OCS_TRY(f->lam.ensure(sizeof(double) * (size_t)(N + 1) * nS * B));
+  OCS_TRY(f->J.ensure(sizeof(double) * B));
+  OCS_TRY(ocs_compute_x_lam_dev(g, p, batch, f->x0.d(), dug.d(), f->xaug.d(), f->lam.d(), f->J.d(), s));
+  OCS_TRY(stage_out_states(f->stage, f->xaug.d(), x, nS, N + 1, batch, s));
+  OCS_TRY(stage_out(f->stage, f->lam.d(), lam, (N + 1) * nS, batch, s));
+  if (J) HIP_TRY(hipMemcpy(J, f->J.p, sizeof(double) * B, hipMemcpyDeviceToHost));
+  return OCS_OK;
 }
 
 }  // extern "C"

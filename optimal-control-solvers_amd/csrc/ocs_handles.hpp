@@ -1,5 +1,7 @@
 // ocs_handles.hpp -- private: handle structs, error plumbing and staging helpers shared by
-// the C-ABI translation units (ocs_api.cpp, ocs_control.cpp, ocs_fbs.cpp).
+// the C-ABI translation units (ocs_api.cpp, ocs_control.cpp, ocs_fbs.cpp, ocs_shooting.cpp, ocs_multi.cpp, ocs_jit.cpp).
+// Ownership: a DevBuf frees its memory when it goes out of scope, a handle struct destroys what it owns in its destructor
+// (streams and events in the body, i.e. before its member buffers go); the ocs_*_destroy entry points are `delete`.
 #pragma once
 #include "../../include/ocs.h"
 
@@ -69,9 +71,25 @@ inline int require_device() {
 // ------------------------------------------------------------------------------------
 // device buffers
 // ------------------------------------------------------------------------------------
+// Owns its memory: freed by the destructor (hipFree waits for the device, so work in flight on the buffer is finished).
+// No object of this type, and no handle that has one, may have static or thread-local storage: its destructor would run at
+// thread or process exit, possibly after the HIP runtime has shut down.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  ~DevBuf() { release(); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.detach(); }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      cap = o.cap;
+      p = o.detach();
+    }
+    return *this;
+  }
   int ensure(size_t bytes) {
     if (bytes <= cap) return OCS_OK;
     if (p) (void)hipFree(p);
@@ -81,13 +99,40 @@ struct DevBuf {
     cap = bytes;
     return OCS_OK;
   }
-  void release() {
+  void release() {   // (for a buffer dropped early on purpose; cleanup is the destructor's)
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
   }
+  void* detach() {   // hands the memory to the caller: this object forgets it
+    void* q = p;
+    p = nullptr;
+    cap = 0;
+    return q;
+  }
   double* d() const { return static_cast<double*>(p); }
 };
+
+// Host staging: a MATLAB-shaped host array (`per` doubles per trajectory, trajectory-major) to / from a batch-minor device
+// array, through the caller's ONE stage buffer on the caller's stream.  stage_out waits for the stream: the host array is
+// complete and the stage buffer free again on return.  stage_in does not wait; a caller whose stage buffer may still be in
+// use waits for its stream first.
+inline int stage_in(DevBuf& stage, DevBuf& dst, const double* host, int per, int batch, hipStream_t s) {
+  const size_t bytes = sizeof(double) * (size_t)per * batch;
+  OCS_TRY(stage.ensure(bytes));
+  OCS_TRY(dst.ensure(bytes));
+  HIP_TRY(hipMemcpyAsync(stage.p, host, bytes, hipMemcpyHostToDevice, s));
+  LAUNCH_TRY(launch_to_batch_minor(stage.d(), dst.d(), per, batch, s));
+  return OCS_OK;
+}
+inline int stage_out(DevBuf& stage, const double* src, double* host, int per, int batch, hipStream_t s) {
+  const size_t bytes = sizeof(double) * (size_t)per * batch;
+  OCS_TRY(stage.ensure(bytes));
+  LAUNCH_TRY(launch_to_traj_major(src, stage.d(), per, batch, s));
+  HIP_TRY(hipMemcpyAsync(host, stage.p, bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return OCS_OK;
+}
 
 // ------------------------------------------------------------------------------------
 // handles
@@ -142,6 +187,10 @@ struct ocs_problem_s {
   // forward-backward-sweep entry points, whose kernels are instantiated per functor (ocs_fbs.cpp: lq_shadow)
   ocs_problem_s* shadow = nullptr;
   unsigned long long shadow_version = 0;
+  ~ocs_problem_s() {
+    delete shadow;
+    if (user) ocs::jit_free(user);
+  }
 };
 
 struct ocs_fbs_state;  // forward-backward-sweep workspace (ocs_fbs.cpp)
@@ -182,6 +231,13 @@ struct ocs_integrator_s {
   // staging for the host entry points
   hipStream_t stream = nullptr;
   DevBuf d_x0, d_u, d_x, d_J, d_lam, d_dJdu, d_lamT, d_stage, d_ck;
+  ~ocs_integrator_s() {
+    if (tc_event) (void)hipEventDestroy(tc_event);
+    delete leg2;
+    if (fbs) ocs_fbs_state_free(fbs);
+    if (lqws) ocs::lq_workspace_free(lqws);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 struct ocs_control_s;

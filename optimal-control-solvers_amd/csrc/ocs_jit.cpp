@@ -127,6 +127,11 @@ struct Compiled {
   std::vector<char> code;
   std::vector<std::string> lowered;
 };
+// (UserModule is a plain struct that the device translation units see too: its owner while it is built or handed on)
+struct ModuleFree {
+  void operator()(UserModule* m) const { jit_free(m); }
+};
+using ModulePtr = std::unique_ptr<UserModule, ModuleFree>;
 
 static unsigned long long fnv1a(const void* data, size_t n, unsigned long long h) {
   const unsigned char* p = (const unsigned char*)data;
@@ -351,7 +356,7 @@ int jit_build(const char* user_src, int nS, int nC, int npar, bool has_cc, bool 
     if (!disk.empty()) disk_cache_write(disk, *fresh);
   }
   slot_lk.unlock();
-  UserModule* m = new UserModule();
+  ModulePtr m(new UserModule());
   m->nS = nS;
   m->nC = nC;
   m->npar = npar;
@@ -365,25 +370,21 @@ int jit_build(const char* user_src, int nS, int nC, int npar, bool has_cc, bool 
   const std::vector<std::string>& lowered = cc->lowered;
   if (load) {
     if (require_device() != OCS_OK) {
-      delete m;
       log = "no HIP device to load the compiled problem on";
       return OCS_ERR_NO_DEVICE;
     }
     if (hipModuleLoadData(&m->mod, m->code.data()) != hipSuccess) {
-      delete m;
       log = "hipModuleLoadData failed";
       return OCS_ERR_HIP;
     }
+    m->loaded = true;   // (from here on jit_free unloads the module)
     for (int k = 0; k < UK_COUNT; ++k)
       if (!names[k].empty() && hipModuleGetFunction(&m->fn[k], m->mod, lowered[k].c_str()) != hipSuccess) {
         log = "kernel " + names[k] + " missing from the compiled module";
-        (void)hipModuleUnload(m->mod);
-        delete m;
         return OCS_ERR_HIP;
       }
-    m->loaded = true;
   }
-  *out = m;
+  *out = m.release();
   return OCS_OK;
 }
 
@@ -428,7 +429,8 @@ int ocs_problem_create_from_source(ocs_problem* out, const char* source, int nS,
     return fail(OCS_ERR_SHAPE, "a problem given as row functions needs nC = 1, nS in {1, 2, 4} and at most 16 parameters");
   const int rc = jit_build(source, nS, nC, nparams, (has_control_char & 1) != 0, true, &m, log, rowsep, (has_control_char & 4) != 0);
   if (rc != OCS_OK) return fail(rc, "user problem: %s", log.substr(0, 400).c_str());
-  ocs_problem_s* p = new ocs_problem_s();
+  std::unique_ptr<ocs_problem_s> owner(new ocs_problem_s());
+  ocs_problem_s* p = owner.get();
   p->id = OCS_PROBLEM_USER;
   p->nS = nS;
   p->nC = nC;
@@ -464,13 +466,9 @@ int ocs_problem_create_from_source(ocs_problem* out, const char* source, int nS,
     }
     int rc2 = ocs_problem_dFdx_times_vec(p, k, t.data(), y.data(), u1.data(), v.data(), g1.data());
     if (rc2 == OCS_OK) rc2 = ocs_problem_dFdx_times_vec(p, k, t.data(), y.data(), u2.data(), v.data(), g2.data());
-    if (rc2 != OCS_OK) {
-      ocs_problem_destroy(p);
-      return rc2;
-    }
+    if (rc2 != OCS_OK) return rc2;
     for (size_t q = 0; q < g1.size(); ++q)
       if (g1[q] != g2[q] && !(std::isnan(g1[q]) && std::isnan(g2[q]))) {
-        ocs_problem_destroy(p);
         return fail(OCS_ERR_INVALID, "flag bit 2 (control from the costate alone) declares that ocs_row_dFdy does not read u, but "
                                      "(dF/dy)' v changes with u (row %d): drop the declaration", (int)(q % nAug));
       }
@@ -480,18 +478,14 @@ int ocs_problem_create_from_source(ocs_problem* out, const char* source, int nS,
     for (double& q : lm) q = rnd() - 0.5;
     rc2 = ocs_problem_ControlChar(p, k, t.data(), x1.data(), lm.data(), c1.data());
     if (rc2 == OCS_OK) rc2 = ocs_problem_ControlChar(p, k, t.data(), x2.data(), lm.data(), c2.data());
-    if (rc2 != OCS_OK) {
-      ocs_problem_destroy(p);
-      return rc2;
-    }
+    if (rc2 != OCS_OK) return rc2;
     for (size_t q = 0; q < c1.size(); ++q)
       if (c1[q] != c2[q] && !(std::isnan(c1[q]) && std::isnan(c2[q]))) {
-        ocs_problem_destroy(p);
         return fail(OCS_ERR_INVALID, "flag bit 2 (control from the costate alone) declares that ocs_ControlChar does not read x, but "
                                      "its value changes with x (control %d): drop the declaration", (int)(q % nC));
       }
   }
-  *out = p;
+  *out = owner.release();
   return OCS_OK;
 }
 

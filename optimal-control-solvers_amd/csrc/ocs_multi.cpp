@@ -144,13 +144,23 @@ struct ocs_multi_s {
   std::vector<int> dev;
   std::vector<hipStream_t> stream;
   std::vector<ncclComm_t> comm;   // empty if there is no communicator (reductions then run on the host)
-  std::vector<double*> d_red;     // per device: [0..3] local {sum, count, min, argmin}, [4..5] all-reduced {sum, count},
+  std::vector<DevBuf> d_red;      // per device: [0..3] local {sum, count, min, argmin}, [4..5] all-reduced {sum, count},
                                   // [6 .. 6 + 2n) all-gathered (min, argmin) pairs
-  std::vector<double*> d_J;       // per device: staging of the shard's J when the entry point keeps none
-  std::vector<size_t> d_J_cap;
+  std::vector<DevBuf> d_J;        // per device: staging of the shard's J when the entry point keeps none
   std::vector<std::unique_ptr<Worker>> worker;   // n > 1 only
   std::string comm_note;          // why there is no communicator, if there is none
   bool stats_pending = false;     // reductions enqueued by a _dev entry point and not fetched yet
+  // (also of a handle that ocs_multi_create gave up half-way: every vector is as long as it got)
+  ~ocs_multi_s() {
+    DeviceGuard guard;
+    for (auto& w : worker) w->stop();
+    for (size_t k = 0; k < dev.size(); ++k) {
+      (void)hipSetDevice(dev[k]);
+      if (k < stream.size() && stream[k]) (void)hipStreamSynchronize(stream[k]);
+      if (k < comm.size() && comm[k] && rccl()) (void)rccl()->CommDestroy(comm[k]);
+      if (k < stream.size() && stream[k]) (void)hipStreamDestroy(stream[k]);
+    }
+  }
 };
 
 namespace {
@@ -202,17 +212,17 @@ int enqueue_reductions(ocs_multi_s* m, const std::vector<const double*>& dJ, con
   const int n = (int)m->dev.size();
   for (int k = 0; k < n; ++k) {
     HIP_TRY(hipSetDevice(m->dev[k]));
-    LAUNCH_TRY(launch_objective_stats(dJ[k], nk[k], lo[k], m->d_red[k], m->stream[k], mask ? (*mask)[k] : nullptr));
+    LAUNCH_TRY(launch_objective_stats(dJ[k], nk[k], lo[k], m->d_red[k].d(), m->stream[k], mask ? (*mask)[k] : nullptr));
   }
   if (!m->comm.empty()) {
     Rccl* r = rccl();
     NCCL_TRY(r->GroupStart());
     for (int k = 0; k < n; ++k)
-      NCCL_TRY(r->AllReduce(m->d_red[k], m->d_red[k] + 4, 2, ncclDouble, ncclSum, m->comm[k], m->stream[k]));
+      NCCL_TRY(r->AllReduce(m->d_red[k].d(), m->d_red[k].d() + 4, 2, ncclDouble, ncclSum, m->comm[k], m->stream[k]));
     NCCL_TRY(r->GroupEnd());
     NCCL_TRY(r->GroupStart());
     for (int k = 0; k < n; ++k)
-      NCCL_TRY(r->AllGather(m->d_red[k] + 2, m->d_red[k] + 6, 2, ncclDouble, m->comm[k], m->stream[k]));
+      NCCL_TRY(r->AllGather(m->d_red[k].d() + 2, m->d_red[k].d() + 6, 2, ncclDouble, m->comm[k], m->stream[k]));
     NCCL_TRY(r->GroupEnd());
   }
   m->stats_pending = true;
@@ -225,7 +235,7 @@ int fetch_reductions(ocs_multi_s* m, double out[4]) {
   std::vector<double> h((size_t)6 + 2 * n);
   if (!m->comm.empty()) {
     HIP_TRY(hipSetDevice(m->dev[0]));
-    HIP_TRY(hipMemcpyAsync(h.data(), m->d_red[0], sizeof(double) * h.size(), hipMemcpyDeviceToHost, m->stream[0]));
+    HIP_TRY(hipMemcpyAsync(h.data(), m->d_red[0].p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, m->stream[0]));
     for (int k = 0; k < n; ++k) {
       HIP_TRY(hipSetDevice(m->dev[k]));
       HIP_TRY(hipStreamSynchronize(m->stream[k]));
@@ -235,7 +245,7 @@ int fetch_reductions(ocs_multi_s* m, double out[4]) {
     for (int k = 0; k < n; ++k) {
       double p[4];
       HIP_TRY(hipSetDevice(m->dev[k]));
-      HIP_TRY(hipMemcpyAsync(p, m->d_red[k], sizeof(p), hipMemcpyDeviceToHost, m->stream[k]));
+      HIP_TRY(hipMemcpyAsync(p, m->d_red[k].p, sizeof(p), hipMemcpyDeviceToHost, m->stream[k]));
       HIP_TRY(hipStreamSynchronize(m->stream[k]));
       h[4] += p[0];
       h[5] += p[1];
@@ -316,34 +326,25 @@ int ocs_multi_create(ocs_multi* out, const int* devices, int n) {
   // then run on the host.
   const char* dup_env = getenv("OCS_MULTI_ALLOW_DUPLICATES");
   const bool allow_dup = dup_env && dup_env[0] == '1';
-  auto* m = new ocs_multi_s;
+  std::unique_ptr<ocs_multi_s> m(new ocs_multi_s);
   bool dup = false;
   for (int k = 0; k < n; ++k) {
     const int d = devices ? devices[k] : k;
-    if (d < 0 || d >= ndev) {
-      delete m;
-      return fail(OCS_ERR_INVALID, "device %d of %d does not exist", d, ndev);
-    }
+    if (d < 0 || d >= ndev) return fail(OCS_ERR_INVALID, "device %d of %d does not exist", d, ndev);
     for (int q : m->dev)
       if (q == d) {
-        if (!allow_dup) {
-          delete m;
-          return fail(OCS_ERR_INVALID, "device %d listed twice", d);
-        }
+        if (!allow_dup) return fail(OCS_ERR_INVALID, "device %d listed twice", d);
         dup = true;
       }
     m->dev.push_back(d);
   }
   m->stream.assign(n, nullptr);
-  m->d_red.assign(n, nullptr);
-  m->d_J.assign(n, nullptr);
-  m->d_J_cap.assign(n, 0);
+  m->d_red.resize(n);
+  m->d_J.resize(n);
   for (int k = 0; k < n; ++k) {
     if (hipSetDevice(m->dev[k]) != hipSuccess || hipStreamCreate(&m->stream[k]) != hipSuccess ||
-        hipMalloc((void**)&m->d_red[k], sizeof(double) * (6 + 2 * (size_t)n)) != hipSuccess) {
-      ocs_multi_destroy(m);
+        m->d_red[k].ensure(sizeof(double) * (6 + 2 * (size_t)n)) != OCS_OK)
       return fail(OCS_ERR_HIP, "stream / buffer creation on device %d failed", m->dev[k]);
-    }
   }
   // one communicator over the local devices; also for n = 1, so that the collective path is the same
   const char* no_env = getenv("OCS_MULTI_NO_RCCL");
@@ -370,23 +371,12 @@ int ocs_multi_create(ocs_multi* out, const int* devices, int n) {
       w->th = std::thread([w] { w->loop(); });
     }
   }
-  *out = m;
+  *out = m.release();
   return OCS_OK;
 }
 
 int ocs_multi_destroy(ocs_multi m) {
-  if (!m) return OCS_OK;
-  DeviceGuard guard;
-  for (auto& w : m->worker) w->stop();
-  for (size_t k = 0; k < m->dev.size(); ++k) {
-    (void)hipSetDevice(m->dev[k]);
-    if (k < m->stream.size() && m->stream[k]) (void)hipStreamSynchronize(m->stream[k]);
-    if (k < m->comm.size() && m->comm[k] && rccl()) (void)rccl()->CommDestroy(m->comm[k]);
-    if (k < m->stream.size() && m->stream[k]) (void)hipStreamDestroy(m->stream[k]);
-    if (k < m->d_red.size() && m->d_red[k]) (void)hipFree(m->d_red[k]);
-    if (k < m->d_J.size() && m->d_J[k]) (void)hipFree(m->d_J[k]);
-  }
-  delete m;
+  delete m;   // (~ocs_multi_s: workers, communicators, streams, then the buffers)
   return OCS_OK;
 }
 
@@ -527,18 +517,12 @@ int ocs_multi_fb_sweep(ocs_multi m, const ocs_integrator* g, const ocs_problem* 
     std::vector<const double*> dJ(n);
     for (int k = 0; k < n; ++k) {
       HIP_TRY(hipSetDevice(m->dev[k]));
-      if (m->d_J_cap[k] < (size_t)nk[k]) {
-        if (m->d_J[k]) (void)hipFree(m->d_J[k]);
-        m->d_J[k] = nullptr;
-        m->d_J_cap[k] = 0;
-        HIP_TRY(hipMalloc((void**)&m->d_J[k], sizeof(double) * nk[k]));
-        m->d_J_cap[k] = nk[k];
-      }
+      OCS_TRY(m->d_J[k].ensure(sizeof(double) * nk[k]));
       std::vector<double> Jk(J + lo[k], J + lo[k] + nk[k]);
       for (int b = 0; b < nk[k]; ++b)
         if (sweeps[lo[k] + b] <= 0) Jk[b] = NAN;
-      HIP_TRY(hipMemcpy(m->d_J[k], Jk.data(), sizeof(double) * nk[k], hipMemcpyHostToDevice));
-      dJ[k] = m->d_J[k];
+      HIP_TRY(hipMemcpy(m->d_J[k].p, Jk.data(), sizeof(double) * nk[k], hipMemcpyHostToDevice));
+      dJ[k] = m->d_J[k].d();
     }
     OCS_TRY(reduce_objectives(m, dJ, nk, lo, stats));
   }

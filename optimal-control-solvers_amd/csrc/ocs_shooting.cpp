@@ -42,12 +42,6 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
   const int nV = nB * nC + nFree;
   const size_t B = (size_t)batch, vb = sizeof(double) * (size_t)nV * B;
   DevBuf gbuf, dbuf, vtbuf, gtbuf, sc, hist, flags, lbub, counter, conv;
-  struct Rel {
-    DevBuf* b[10];
-    ~Rel() {
-      for (DevBuf* q : b) q->release();
-    }
-  } rel{{&gbuf, &dbuf, &vtbuf, &gtbuf, &sc, &hist, &flags, &lbub, &counter, &conv}};
   OCS_TRY(gbuf.ensure(vb));
   OCS_TRY(dbuf.ensure(vb));
   OCS_TRY(vtbuf.ensure(vb));
