@@ -162,6 +162,26 @@ int ocs_integrator_nsteps(ocs_integrator g, int *nsteps); /* obj.nSTEPS */
 #define OCS_MAPPING_PIPELINE 3
 #define OCS_MAPPING_SCAN 4
 int ocs_integrator_set_mapping(ocs_integrator g, int mapping);
+/* Device layout of the per-step arrays of ocs_compute_states_dev / ocs_compute_adjoints_dev on this handle (no counterpart in
+ * the reference): x / checkpoints and lam (cols = N+1, rows = nAug), u and dJdu (cols = 2N+1, rows = nC).
+ *   OCS_LAYOUT_BATCH_MINOR (default)  [cols][rows][batch]
+ *   OCS_LAYOUT_TILED                  trajectories in tiles of 16: element (column i, row r, trajectory b) at double index
+ *                                     ((b / 16) * cols + i) * rows * 16 + r * 16 + b % 16, so one row of a tile is one 128-byte
+ *                                     line and a tile's stream over time is sequential in memory.  An array holds
+ *                                     ceil(batch / 16) * 16 trajectories (ocs_tiled_doubles); the pad lanes of the last tile
+ *                                     may hold anything on input, NaN included, hold unspecified values on output, and never
+ *                                     reach a trajectory's result.  x0, J, lamT stay [rows][batch].
+ * Tiled arrays are for callers that keep x, u, lam, dJdu on the device across many calls; ocs_to_tiled_dev /
+ * ocs_from_tiled_dev convert.  The tiled layout covers the registry logistic problems with 1, 2 or 4 states and shared
+ * parameters on an RK4Integrator, in the automatic, pipeline and scan mappings (it runs the pipeline state pass and the scan
+ * adjoint pass at every batch, any N >= 1).  Everything else -- the LQ problem, plugin problems, nS = 3, per-trajectory
+ * parameters, RK4InfiniteIntegrator, the lane and row-split mappings, the host-array entry points, ocs_nlp_objective*,
+ * ocs_fb_sweep*, ocs_compute_x_lam*, ocs_single_shooting*, ocs_multi_* -- fails with OCS_ERR_UNSUPPORTED at the compute call
+ * while the handle is set to it.  Results are the batch-minor layout's bit for bit. */
+#define OCS_LAYOUT_BATCH_MINOR 0
+#define OCS_LAYOUT_TILED 1
+int ocs_integrator_set_layout(ocs_integrator g, int layout);
+int ocs_integrator_layout(ocs_integrator g);
 int ocs_integrator_t(ocs_integrator g, double *t);        /* obj.t, 2N+1 values */
 int ocs_integrator_h(ocs_integrator g, double *h);        /* obj.h, N values    */
 
@@ -416,6 +436,12 @@ int ocs_device_download(void *dst_host, const void *src_device, unsigned long by
 /* layout helpers: MATLAB (trajectory-major, [batch][cols][rows]) <-> batch-minor ([cols][rows][batch]),
  * device pointers, rows*cols doubles per trajectory. */
 int ocs_to_batch_minor_dev(const double *src, double *dst, int per_traj, int batch, void *stream);
+/* batch-minor [cols][rows][batch] <-> OCS_LAYOUT_TILED (ocs_integrator_set_layout), coalesced on both sides; dst holds
+ * ocs_tiled_doubles(rows, cols, batch) doubles (to) / cols * rows * batch (from).  ocs_to_tiled_dev fills the pad lanes of the
+ * last tile with a copy of the last trajectory. */
+int ocs_to_tiled_dev(const double *src, double *dst, int rows, int cols, int batch, void *stream);
+int ocs_from_tiled_dev(const double *src, double *dst, int rows, int cols, int batch, void *stream);
+long ocs_tiled_doubles(int rows, int cols, int batch); /* host: cols * rows * 16 * ceil(batch / 16); OCS_ERR_INVALID if an argument is < 1 */
 int ocs_to_traj_major_dev(const double *src, double *dst, int per_traj, int batch, void *stream);
 /* dst[0..n) = src[0..n) with this path's access width (8 B per lane): the known-byte-count launch used
  * to calibrate the rocprofv3 HBM counters (scripts/calibrate_traffic.py). */

@@ -15,6 +15,7 @@ def tracing_enabled():
 
 from .problem import OCProblem, TestOCProblem, LogisticProblem, LQProblem, UserProblem  # noqa: F401
 from .integrator import Integrator, RK4Integrator, RK4InfiniteIntegrator, trajectory_status_dev  # noqa: F401
+from .integrator import TILE, tiled_doubles, tiled_index, to_tiled, from_tiled  # noqa: F401
 from .control import Control, PWLinearControl, PWConstantControl, ChebyshevControl  # noqa: F401
 from .interp import vectorInterpolant, vectorInterpolant_dev, heval, linspace  # noqa: F401
 from .solvers import (nlp_objective, nlp_objective_dev, single_shooting, single_shooting_batch,  # noqa: F401

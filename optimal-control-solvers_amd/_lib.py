@@ -63,6 +63,8 @@ _SIG = {
     "ocs_rk4_create": (C.c_int, [C.POINTER(vp), dp, C.c_int]),
     "ocs_integrator_destroy": (C.c_int, [vp]),
     "ocs_integrator_set_mapping": (C.c_int, [vp, C.c_int]),
+    "ocs_integrator_set_layout": (C.c_int, [vp, C.c_int]),
+    "ocs_integrator_layout": (C.c_int, [vp]),
     "ocs_control_set_fusion": (C.c_int, [vp, C.c_int]),
     "ocs_integrator_nsteps": (C.c_int, [vp, ip]),
     "ocs_integrator_t": (C.c_int, [vp, dp]),
@@ -124,6 +126,9 @@ _SIG = {
     "ocs_copy_dev": (C.c_int, [vp, vp, C.c_long, vp]),
     "ocs_to_batch_minor_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     "ocs_to_traj_major_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "ocs_to_tiled_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ocs_from_tiled_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ocs_tiled_doubles": (C.c_long, [C.c_int, C.c_int, C.c_int]),
 }
 
 for _name, (_res, _args) in _SIG.items():

@@ -291,6 +291,29 @@ int ocs_integrator_set_mapping(ocs_integrator g, int mapping) {
   if (g->leg2) g->leg2->mapping = mapping;
   return OCS_OK;
 }
+int ocs_integrator_set_layout(ocs_integrator g, int layout) {
+  if (!g) return fail(OCS_ERR_INVALID, "null integrator");
+  if (layout != OCS_LAYOUT_BATCH_MINOR && layout != OCS_LAYOUT_TILED) return fail(OCS_ERR_INVALID, "layout must be 0 or 1");
+  g->layout = layout;   // (what the tiled layout does not cover is refused at the compute call, as for set_mapping)
+  return OCS_OK;
+}
+int ocs_integrator_layout(ocs_integrator g) { return g ? g->layout : fail(OCS_ERR_INVALID, "null integrator"); }
+// what the tiled layout covers: the registry logistic family with 1, 2 or 4 states and shared parameters, on an RK4Integrator,
+// in the automatic / pipeline / scan mappings (pipeline + scan at every batch, remainder steps on the lane kernels)
+static int tiled_check(const ocs_integrator_s* g, const ocs_problem_s* p) {
+  if (g->layout != LAYOUT_TILED) return OCS_OK;
+  const char* why = nullptr;
+  if (g->kind != 0) why = "RK4InfiniteIntegrator";
+  else if (p->functor == Functor::LQ) why = "the LQ problem";
+  else if (p->functor == Functor::User) why = "hipRTC plugin problems";
+  else if (p->nS == 3) why = "nS = 3 (the wave-specialised kernels take 1, 2 or 4 states)";
+  else if (p->pmask || p->has_w) why = "per-trajectory parameters";
+  else if (g->mapping != MAP_AUTO && g->mapping != MAP_PIPELINE && g->mapping != MAP_SCAN)
+    why = "the lane and row-split mappings (automatic, pipeline or scan only)";
+  else if (!tiled_supported(describe(p))) why = "this problem";
+  if (why) return fail(OCS_ERR_UNSUPPORTED, "tiled layout: not instantiated for %s", why);
+  return OCS_OK;
+}
 int ocs_integrator_nsteps(ocs_integrator g, int* nsteps) {
   if (!g || !nsteps) return fail(OCS_ERR_INVALID, "null argument");
   *nsteps = g->N;
@@ -310,19 +333,24 @@ int ocs_integrator_h(ocs_integrator g, double* h) {
 // one RK4 leg, forward.  ck receives the checkpoints (x itself when the caller wants x).
 static int leg_forward(ocs_integrator_s* g, ocs_problem_s* p, int batch, const double* x0, const double* u,
                        double* x, double* J, const FwdOpts& o, hipStream_t s) {
+  OCS_TRY(tiled_check(g, p));
   OCS_TRY(bind_problem(g, p, batch, s));
+  const size_t ckdbl = g->layout == LAYOUT_TILED ? tiled_doubles_host((size_t)p->nS + 1, (size_t)g->N + 1, (size_t)batch)
+                                                 : (size_t)(p->nS + 1) * (g->N + 1) * batch;
   double* ck = x;
   if (!ck && (g->kind == 1 || o.uconst || g->want_ck)) {
     // checkpoints go to handle-owned scratch so the adjoint pass can still run
-    OCS_TRY(g->d_ck.ensure(sizeof(double) * (size_t)(p->nS + 1) * (g->N + 1) * batch));
+    OCS_TRY(g->d_ck.ensure(sizeof(double) * ckdbl));
     ck = g->d_ck.d();
   }
   g->ck = nullptr;
   FwdOpts om = o;
   om.mapping = g->mapping;
+  om.layout = g->layout;
   LAUNCH_TRY(launch_forward(describe(p), describe(g), batch, x0, u, ck, J, om, s));
   g->ck = ck;
   g->ck_batch = batch;
+  g->ck_layout = g->layout;
   g->ck_prob = p;
   return OCS_OK;
 }
@@ -371,12 +399,14 @@ int ocs_compute_adjoints_dev(ocs_integrator g, ocs_problem p, int batch, const d
   OCS_TRACE("ocs_compute_adjoints_dev");
   if (!g || !p || !u) return fail(OCS_ERR_INVALID, "null argument");
   if (!lam && !dJdu) return fail(OCS_ERR_INVALID, "at least one of lam, dJdu must be requested");
-  if (!g->ck || g->ck_prob != p || g->ck_batch != batch)
-    return fail(OCS_ERR_ORDER, "compute_adjoints needs compute_states first on the same handle/problem/batch");
+  if (!g->ck || g->ck_prob != p || g->ck_batch != batch || g->ck_layout != g->layout)
+    return fail(OCS_ERR_ORDER, "compute_adjoints needs compute_states first on the same handle/problem/batch/layout");
   hipStream_t s = (hipStream_t)stream;
+  OCS_TRY(tiled_check(g, p));
   OCS_TRY(bind_problem(g, p, batch, s));
   BwdOpts o;
   o.mapping = g->mapping;
+  o.layout = g->layout;
   o.lam0 = g->want_lam0;
   if (!lam) {
     OCS_TRY(g->d_split.ensure(sizeof(double) * (size_t)(p->nS + 1) * batch));
@@ -416,6 +446,7 @@ int ocs_compute_states(ocs_integrator g, ocs_problem p, int batch, const double*
   OCS_TRACE("ocs_compute_states");
   if (!g || !p || !x0 || !u || !J) return fail(OCS_ERR_INVALID, "null argument");
   if (batch < 1) return fail(OCS_ERR_SHAPE, "batch must be >= 1");
+  OCS_TRY(refuse_tiled(g, "ocs_compute_states (host arrays)"));
   OCS_TRY(upload_grid(g));
   const int nAug = p->nS + 1, nC = p->nC, N = g->N;
   HIP_TRY(hipStreamSynchronize(g->stream));
@@ -460,6 +491,7 @@ int ocs_compute_adjoints(ocs_integrator g, ocs_problem p, int batch, const doubl
                          double* lam, double* dJdu) {
   OCS_TRACE("ocs_compute_adjoints");
   if (!g || !p || !u || !lam) return fail(OCS_ERR_INVALID, "null argument");
+  OCS_TRY(refuse_tiled(g, "ocs_compute_adjoints (host arrays)"));
   if (!g->ck || g->ck != g->d_x.d() || g->ck_prob != p || g->ck_batch != batch)
     return fail(OCS_ERR_ORDER, "compute_adjoints needs compute_states first on the same handle/problem/batch");
   const int nAug = p->nS + 1, nC = p->nC, N = g->N;
@@ -515,6 +547,22 @@ int ocs_to_batch_minor_dev(const double* src, double* dst, int per_traj, int bat
   OCS_TRY(require_device());
   LAUNCH_TRY(launch_to_batch_minor(src, dst, per_traj, batch, (hipStream_t)stream));
   return OCS_OK;
+}
+int ocs_to_tiled_dev(const double* src, double* dst, int rows, int cols, int batch, void* stream) {
+  if (!src || !dst || rows < 1 || cols < 1 || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  OCS_TRY(require_device());
+  LAUNCH_TRY(launch_tiled_convert(true, src, dst, (size_t)rows * cols, batch, (hipStream_t)stream));
+  return OCS_OK;
+}
+int ocs_from_tiled_dev(const double* src, double* dst, int rows, int cols, int batch, void* stream) {
+  if (!src || !dst || rows < 1 || cols < 1 || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  OCS_TRY(require_device());
+  LAUNCH_TRY(launch_tiled_convert(false, src, dst, (size_t)rows * cols, batch, (hipStream_t)stream));
+  return OCS_OK;
+}
+long ocs_tiled_doubles(int rows, int cols, int batch) {
+  if (rows < 1 || cols < 1 || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  return (long)tiled_doubles_host((size_t)rows, (size_t)cols, (size_t)batch);
 }
 int ocs_to_traj_major_dev(const double* src, double* dst, int per_traj, int batch, void* stream) {
   if (!src || !dst || per_traj < 1 || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");

@@ -439,6 +439,7 @@ int ocs_control_eval_uFunc(ocs_control c, const double* v, int nq, const double*
 // FreeInitStates is a host array of 1-based state indices like MATLAB's.
 int ocs_nlp_objective_dev(ocs_integrator g, ocs_problem p, ocs_control c, int batch, double* x0, const double* v,
                           int nFree, const int* FreeInitStates, double* J, double* dJdv, void* stream) {
+  OCS_TRY(refuse_tiled(g, "ocs_nlp_objective"));
   OCS_TRACE("ocs_nlp_objective_dev");
   if (!g || !p || !c || !x0 || !v || !J || !dJdv || batch < 1 || nFree < 0 || (nFree > 0 && !FreeInitStates))
     return fail(OCS_ERR_INVALID, "bad argument");

@@ -19,6 +19,39 @@ __device__ static inline int tile_base(int block, int TPW, int batch) {
   return b0 + TPW <= batch ? b0 : batch - TPW;
 }
 
+// ---------------------------------------------------------------------------------------
+// device layouts of the per-step arrays (x / checkpoints, u, lam, dJdu): THE copy of the index arithmetic
+// ---------------------------------------------------------------------------------------
+// An array of `cols` columns (time) x `rows` rows x `batch` trajectories lives either batch-minor, element (i, r, b) at
+// (i rows + r) batch + b, or tiled (OCS_LAYOUT_TILED): trajectories in tiles of kTile = 16, one row of a tile one 128-byte
+// line, element (i, r, b) at ((b / 16) cols + i) rows 16 + r 16 + b % 16 -- everything a workgroup streams over time is one
+// sequential run of rows * 128 bytes per column.  In both layouts the rows of consecutive columns follow each other at one
+// stride, row(), so the kernels walk an array row by row with one pointer whatever the column; what differs is the stride
+// and the trajectory's part of the index, at(b).  A tiled array holds whole tiles: ceil(batch / 16) * 16 trajectories.
+// Per-trajectory vectors (x0, J, lamT, lam0) are [rows][batch] in both layouts.
+constexpr int kTile = 16;
+__host__ __device__ constexpr size_t tiled_tiles(size_t batch) { return (batch + kTile - 1) / kTile; }
+__host__ __device__ constexpr size_t tiled_tile_doubles(size_t rows, size_t cols) { return cols * rows * kTile; }
+__host__ __device__ constexpr size_t tiled_doubles(size_t rows, size_t cols, size_t batch) {
+  return tiled_tiles(batch) * tiled_tile_doubles(rows, cols);
+}
+__host__ __device__ constexpr size_t tiled_index(size_t rows, size_t cols, size_t i, size_t r, size_t b) {
+  return ((b / kTile) * cols + i) * rows * kTile + r * kTile + b % kTile;
+}
+template <bool TILED>
+struct DevLayout {
+  size_t s;   // batch-minor: the batch; tiled: doubles per tile, cols * rows * 16
+  // cols: the columns of the WHOLE array, also where a launch is handed a pointer to one of its later columns
+  __host__ __device__ static inline DevLayout make(size_t batch, size_t rows, size_t cols) {
+    return DevLayout{TILED ? tiled_tile_doubles(rows, cols) : batch};
+  }
+  __host__ __device__ inline size_t row() const { return TILED ? (size_t)kTile : s; }
+  __host__ __device__ inline size_t at(size_t b) const { return TILED ? (b / kTile) * s + b % kTile : b; }
+  // the same relative to trajectory b0 (a multiple of 16: the first of a workgroup): the part of a workgroup's lanes, small
+  // enough for the 32-bit lane offsets of the raw buffer accesses whatever the batch
+  __host__ __device__ inline size_t at(size_t b, size_t b0) const { return at(b) - at(b0); }
+};
+
 // Wave-uniform read-only tables (step sizes, time coefficients, shared parameters) are read
 // through the constant address space so the backend emits scalar (s_load) instead of
 // per-lane vector loads: `__restrict__` on struct members does not reach alias analysis.

@@ -418,6 +418,7 @@ int ocs_problem_ControlChar(ocs_problem p, int k, const double* t, const double*
 // augmented system of compute_x_lam_J.m:6-15), lam [N+1][nS][B], J [B] (may be NULL).
 int ocs_compute_x_lam_dev(ocs_integrator g, ocs_problem p, int batch, const double* x0, const double* ugrid,
                           double* xaug, double* lam, double* J, void* stream) {
+  OCS_TRY(refuse_tiled(g, "ocs_compute_x_lam"));
   OCS_TRACE("ocs_compute_x_lam_dev");
   if (!g || !p || !x0 || !ugrid || !xaug || !lam || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
   if (g->kind != 0) return fail(OCS_ERR_UNSUPPORTED, "compute_x_lam needs an RK4Integrator grid");
@@ -468,6 +469,7 @@ int ocs_compute_x_lam_dev(ocs_integrator g, ocs_problem p, int batch, const doub
 int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x0, const ocs_fbs_options* opt,
                      const double* u0grid, const double* u0err, double* xaug, double* lam, double* uInterp,
                      double* J, int* sweeps, double* maxChange, void* stream) {
+  OCS_TRY(refuse_tiled(g, "ocs_fb_sweep"));
   OCS_TRACE("ocs_fb_sweep_dev");
   if (!g || !p || !x0 || !opt || !xaug || !lam || !uInterp || !J || !sweeps || batch < 1)
     return fail(OCS_ERR_INVALID, "bad argument");

@@ -207,6 +207,7 @@ struct ocs_integrator_s {
   hipStream_t tc_stream = nullptr; // ... on this stream: a call on another stream waits for it first
   std::vector<int> traj_status;    // per-trajectory flags of the last host compute_states / nlp_objective
   int mapping = 0;  // ocs::Mapping requested through ocs_integrator_set_mapping (0 = automatic)
+  int layout = 0;   // ocs::Layout of the per-step device arrays of the _dev compute calls (ocs_integrator_set_layout)
   int kind = 0;  // 0 RK4Integrator, 1 RK4InfiniteIntegrator (then `leg2` and `ustar` are set)
   ocs_integrator_s* leg2 = nullptr;   // integrator2 of RK4InfiniteIntegrator.m:13-14
   std::vector<double> ustar;          // uStar (nC)
@@ -227,6 +228,7 @@ struct ocs_integrator_s {
   // state of the last forward pass (the xK contract of RK4Integrator.m:10,32)
   const double* ck = nullptr;
   int ck_batch = 0;
+  int ck_layout = 0;            // the layout the checkpoints were written in
   const ocs_problem_s* ck_prob = nullptr;
   // staging for the host entry points
   hipStream_t stream = nullptr;
@@ -245,6 +247,14 @@ const double* ocs_control_device_J(const ocs_control_s* c);   // ocs_control.cpp
 int ocs_control_device_id(const ocs_control_s* c);             // device owning the handle's memory, -1 before the first use
 
 namespace ocs {
+
+// Entry points that read or write per-step arrays in the batch-minor layout only: refused on a handle set to the tiled layout
+inline int refuse_tiled(const ocs_integrator_s* g, const char* what) {
+  if (g && g->layout != LAYOUT_BATCH_MINOR)
+    return fail(OCS_ERR_UNSUPPORTED, "%s: the integrator is set to the tiled layout, which only ocs_compute_states_dev / "
+                "ocs_compute_adjoints_dev read and write (ocs_integrator_set_layout)", what);
+  return OCS_OK;
+}
 
 inline int upload_problem(ocs_problem_s* p) {
   if (p->uploaded) return OCS_OK;

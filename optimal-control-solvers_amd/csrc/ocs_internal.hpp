@@ -132,6 +132,19 @@ int launch_forward_rs(const ProblemDesc& p, const GridDesc& g, int batch, const 
 int launch_backward_rs(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
                        const double* lamT, double* lam, double* dJdu, double* lam0, hipStream_t s);
 
+// the pass pair on tiled arrays (OCS_LAYOUT_TILED; index map: ocs_device_common.hpp): registry logistic problems with 1, 2 or 4
+// states and shared parameters.  g.N: the steps of this launch, whole blocks (8) / chunks (scan_chunk_steps()) from step 0;
+// nodes: N + 1 of the whole pass; x / u / xck / lam / dJdu: the whole tiled arrays
+int launch_forward_p2_tiled(const ProblemDesc& p, const GridDesc& g, int nodes, int batch, const double* x0,
+                            const double* u, double* x, double* J, hipStream_t s);
+int launch_backward_scan_tiled(const ProblemDesc& p, const GridDesc& g, int nodes, int batch, const double* xck,
+                               const double* u, const double* lamT, bool lamT_col, double* lam, double* dJdu, double* lam0,
+                               const double* pend0, hipStream_t s);
+// batch-minor [nR][batch] <-> tiled, nR = cols * rows
+int launch_tiled_convert(bool to_tiled, const double* src, double* dst, size_t nR, int batch, hipStream_t s);
+size_t tiled_doubles_host(size_t rows, size_t cols, size_t batch);
+bool tiled_supported(const ProblemDesc& p);
+enum Layout : int { LAYOUT_BATCH_MINOR = 0, LAYOUT_TILED = 1 };
 struct FwdOpts;
 struct BwdOpts;
 // matrix-core kernels of the shared-Jacobian linear-quadratic problem (ocs_lq_kernels.hip)
@@ -164,12 +177,14 @@ struct FwdOpts {
                                 // forward_gate_supported says so; otherwise the call fails)
   bool no_cost_row = false;     // the running-objective row of x may be left unwritten (only J is wanted); honoured
                                 // where it saves traffic (the pipeline kernel), ignored elsewhere
+  int layout = LAYOUT_BATCH_MINOR;  // of x and u; tiled: plain passes only (none of the options above), pipeline + lane remainder
 };
 struct BwdOpts {
   int mapping = MAP_AUTO;
   bool uconst = false;
   double* lam0 = nullptr;       // [nAug][B]: lam(:,1)
   double* split_scratch = nullptr;  // [nAug][B]: hand-over column of a split pass when no lam array is requested
+  int layout = LAYOUT_BATCH_MINOR;  // of xck, u, lam and dJdu; tiled: plain passes only, scan + lane remainder
 };
 int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                    double* x, double* J, const FwdOpts& o, hipStream_t s);

@@ -212,10 +212,80 @@ bool tail_leg_wave_ok(const ProblemDesc& p, const GridDesc& g, int batch) {
   if (p.functor == Functor::LQ) return false;
   return choose_mapping(p, g.N, batch, MAP_AUTO, true, false, true) == MAP_PIPELINE;
 }
+// ---------------------------------------------------------------------------------------
+// the pass pair on tiled arrays: pipeline + scan at every batch, the steps past the last whole block / chunk on the lane kernels
+// ---------------------------------------------------------------------------------------
+bool tiled_supported(const ProblemDesc& p) {
+  return pipeline_supported(p.functor, p.nS, p.nC) && scan_supported(p.functor, p.nS, p.nC) && !p.pb;
+}
+template <class P>
+static void run_forward_tiled(const FwdArgsTiled& t, hipStream_t s) {
+  const dim3 grid((t.a.batch + 63) / 64), block(64);
+  if (t.a.x)
+    k_forward_tiled<P, kChunk, pf_of<P>(), true><<<grid, block, 0, s>>>(t);
+  else
+    k_forward_tiled<P, kChunk, pf_of<P>(), false><<<grid, block, 0, s>>>(t);
+}
+template <class P>
+static void run_backward_tiled(const BwdArgsTiled& t, hipStream_t s) {
+  const dim3 grid((t.a.batch + 63) / 64), block(64);
+  if (t.a.lam && t.a.dJdu)
+    k_backward_tiled<P, kChunk, pf_of<P>(), true, true><<<grid, block, 0, s>>>(t);
+  else if (t.a.lam)
+    k_backward_tiled<P, kChunk, pf_of<P>(), true, false><<<grid, block, 0, s>>>(t);
+  else
+    k_backward_tiled<P, kChunk, pf_of<P>(), false, true><<<grid, block, 0, s>>>(t);
+}
+static int launch_forward_tiled(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
+                                double* x, double* J, const FwdOpts& o, hipStream_t s) {
+  const bool map_ok = o.mapping == MAP_AUTO || o.mapping == MAP_PIPELINE || o.mapping == MAP_SCAN;
+  if (!tiled_supported(p) || !map_ok || o.uconst || o.Jadd || o.frozen || o.gate || g.N < 1 || batch < 1) return -1;
+  const int D = pipeline_block_steps(), N1 = (g.N / D) * D, nodes = g.N + 1;
+  if (N1 > 0 && N1 < g.N && !x) return -1;   // the split needs the boundary column in memory
+  if (N1 > 0) {
+    GridDesc g1 = g;
+    g1.N = N1;
+    const int rc = launch_forward_p2_tiled(p, g1, nodes, batch, x0, u, x, J, s);
+    if (rc || N1 == g.N) return rc;
+  }
+  // steps N1 .. N-1 on the lane kernel, continuing from column N1 of the tiled x (N1 = 0: the whole pass, from x0)
+  const size_t xrow = kTile, xcol = (size_t)(p.nS + 1) * kTile, ucol = (size_t)p.nC * kTile;
+  double* xb = x ? x + (size_t)N1 * xcol : nullptr;
+  const FwdArgs a{g.N - N1, batch, g.REC + (size_t)N1 * rec_stride_host(functor_ntc(p.functor, p.nS)), p.ps, nullptr, 0u,
+                  N1 > 0 ? xb : x0, u + (size_t)(2 * N1) * ucol, xb, J, nullptr, nullptr, nullptr,
+                  N1 > 0 ? xb + (size_t)p.nS * xrow : nullptr};
+  const FwdArgsTiled t{a, nodes, N1 > 0 ? 1 : 0};
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_forward_tiled<decltype(P)>(t, s); })) return -1;
+  return hip_rc(hipGetLastError());
+}
+static int launch_backward_tiled(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
+                                 const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s) {
+  const bool map_ok = o.mapping == MAP_AUTO || o.mapping == MAP_PIPELINE || o.mapping == MAP_SCAN;
+  if (!tiled_supported(p) || !map_ok || o.uconst || (!lam && !dJdu) || g.N < 1 || batch < 1) return -1;
+  const int Ls = scan_chunk_steps(), N1 = (g.N / Ls) * Ls, nodes = g.N + 1;
+  if (N1 == g.N) return launch_backward_scan_tiled(p, g, nodes, batch, xck, u, lamT, false, lam, dJdu, o.lam0, nullptr, s);
+  if (N1 > 0 && !lam && !o.split_scratch) return -1;
+  // steps N-1 .. N1 first, on the lane kernel (as split_at of launch_backward): lam columns N1 .. N, dJdu columns 2 N1 .. 2 N
+  const size_t xcol = (size_t)(p.nS + 1) * kTile, ucol = (size_t)p.nC * kTile;
+  double* lamb = lam ? lam + (size_t)N1 * xcol : o.split_scratch;   // lam(:, N1): a tiled column, or a [nAug][B] vector
+  double* db = dJdu ? dJdu + (size_t)(2 * N1) * ucol : nullptr;
+  const BwdArgs a{g.N - N1, batch, g.REC + (size_t)N1 * rec_stride_host(functor_ntc(p.functor, p.nS)), p.ps, nullptr, 0u,
+                  xck + (size_t)N1 * xcol, u + (size_t)(2 * N1) * ucol, lamT, lam ? lamb : nullptr, db,
+                  N1 == 0 ? o.lam0 : (lam ? nullptr : lamb)};
+  const BwdArgsTiled t{a, nodes};
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_backward_tiled<decltype(P)>(t, s); })) return -1;
+  const int rc = hip_rc(hipGetLastError());
+  if (rc || N1 == 0) return rc;
+  GridDesc g1 = g;
+  g1.N = N1;
+  return launch_backward_scan_tiled(p, g1, nodes, batch, xck, u, lamb, lam != nullptr, lam, dJdu, o.lam0, db, s);
+}
+
 // FwdOpts::gate: honoured by any state pass the sweep launches with `frozen` set (pipeline kernels, split passes, the lane
 // kernel), refused on the LQ functor (the sweep runs that problem's plugin twin or its own matrix-core passes)
 int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                    double* x, double* J, const FwdOpts& o, hipStream_t s) {
+  if (o.layout == LAYOUT_TILED) return launch_forward_tiled(p, g, batch, x0, u, x, J, o, s);
   if (o.gate && (o.mapping != MAP_AUTO || o.uconst || o.Jadd || p.functor == Functor::LQ || !o.frozen)) return -1;
   if (p.functor == Functor::LQ) return launch_forward_lq(p, g, batch, x0, u, x, J, o, s);
   const bool plain = !o.uconst && !o.Jadd;
@@ -289,6 +359,7 @@ static void run_backward(const BwdArgs& a, bool uconst, hipStream_t s) {
 }
 int launch_backward(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
                     const double* lamT, double* lam, double* dJdu, const BwdOpts& o, hipStream_t s) {
+  if (o.layout == LAYOUT_TILED) return launch_backward_tiled(p, g, batch, xck, u, lamT, lam, dJdu, o, s);
   if (p.functor == Functor::LQ) return launch_backward_lq(p, g, batch, xck, u, lamT, lam, dJdu, o, s);
   const bool plain = !o.uconst;
   int map = choose_mapping(p, g.N, batch, o.mapping, plain, true, lam != nullptr);
@@ -411,6 +482,49 @@ int launch_to_traj_major(const double* src, double* dst, int per, int batch, hip
                      batch);
   return hip_rc(hipGetLastError());
 }
+
+// batch-minor [nR][batch] (nR = cols * rows) <-> tiled [tiles][nR][16] (ocs_device_common.hpp).  A workgroup moves 64 rows of
+// four tiles through LDS: on the batch-minor side a wave touches 64 consecutive trajectories of a row (512 bytes), on the
+// tiled side the 64 rows of a tile in one run (8 KiB).  TO: the pad lanes of the last tile get the last trajectory.
+template <bool TO>
+__global__ __launch_bounds__(256) void k_tiled_convert(const double* __restrict__ src, double* __restrict__ dst, int nR,
+                                                       int batch) {
+  __shared__ double tile[64][65];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int R0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
+  const int ntiles = (int)tiled_tiles((size_t)batch);
+  const size_t ts = (size_t)nR * kTile;
+  if (TO) {
+    const int b = b0 + tx < batch ? b0 + tx : batch - 1;
+    for (int rr = ty; rr < 64; rr += 4)
+      if (R0 + rr < nR) tile[rr][tx] = src[(size_t)(R0 + rr) * batch + b];
+  } else {
+    for (int k = threadIdx.x; k < 4 * 64 * kTile; k += 256) {
+      const int tq = k / (64 * kTile), rr = (k / kTile) % 64, l = k % kTile, t = b0 / kTile + tq;
+      if (t < ntiles && R0 + rr < nR) tile[rr][tq * kTile + l] = src[(size_t)t * ts + (size_t)(R0 + rr) * kTile + l];
+    }
+  }
+  __syncthreads();
+  if (TO) {
+    for (int k = threadIdx.x; k < 4 * 64 * kTile; k += 256) {
+      const int tq = k / (64 * kTile), rr = (k / kTile) % 64, l = k % kTile, t = b0 / kTile + tq;
+      if (t < ntiles && R0 + rr < nR) dst[(size_t)t * ts + (size_t)(R0 + rr) * kTile + l] = tile[rr][tq * kTile + l];
+    }
+  } else {
+    for (int rr = ty; rr < 64; rr += 4)
+      if (R0 + rr < nR && b0 + tx < batch) dst[(size_t)(R0 + rr) * batch + b0 + tx] = tile[rr][tx];
+  }
+}
+int launch_tiled_convert(bool to_tiled, const double* src, double* dst, size_t nR, int batch, hipStream_t s) {
+  const dim3 grid((unsigned)((nR + 63) / 64), (unsigned)((batch + 63) / 64));
+  if (nR > 0x7fffffff || grid.y > 65535) return -1;
+  if (to_tiled)
+    k_tiled_convert<true><<<grid, dim3(256), 0, s>>>(src, dst, (int)nR, batch);
+  else
+    k_tiled_convert<false><<<grid, dim3(256), 0, s>>>(src, dst, (int)nR, batch);
+  return hip_rc(hipGetLastError());
+}
+size_t tiled_doubles_host(size_t rows, size_t cols, size_t batch) { return tiled_doubles(rows, cols, batch); }
 
 __global__ void k_traj_status(const double* __restrict__ J, int n, int* __restrict__ status) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

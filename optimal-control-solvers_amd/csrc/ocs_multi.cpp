@@ -278,6 +278,7 @@ int check_handles(ocs_multi_s* m, const ocs_integrator* g, const ocs_problem* p,
   if (!g || !p) return fail(OCS_ERR_INVALID, "null handle array");
   for (size_t k = 0; k < m->dev.size(); ++k) {
     if (!g[k] || !p[k] || (c && !c[k])) return fail(OCS_ERR_INVALID, "null handle for device %d", m->dev[k]);
+    OCS_TRY(refuse_tiled(g[k], "ocs_multi_*"));
     const int dg = g[k]->device, dp = p[k]->device, dc = c ? ocs_control_device_id(c[k]) : -1;
     if ((dg >= 0 && dg != m->dev[k]) || (dp >= 0 && dp != m->dev[k]) || (dc >= 0 && dc != m->dev[k]))
       return fail(OCS_ERR_INVALID, "slot %d runs on device %d, but its handles live on device %d (create them under "

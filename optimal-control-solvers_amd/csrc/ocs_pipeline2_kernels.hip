@@ -72,6 +72,30 @@ static void run_forward_p2(const FwdArgsP2& a, bool uniform, hipStream_t s) {
     run_forward_p2u<P, false>(a, s);
 }
 
+// the same pass on tiled x and u: g.N whole blocks of a pass of `nodes` - 1 steps, any batch (no workgroup overlaps another)
+template <class P>
+static void run_forward_p2_tiled(const FwdArgsP2Tiled& t, bool uniform, hipStream_t s) {
+  using C_ = P2Cfg<P::NS>;
+  const dim3 grid((t.a.batch + C_::TPW - 1) / C_::TPW), block(C_::NWAVE * 64);
+  const size_t lds_pad = (P::NS == 1) ? 0 : 48 * 1024;   // (one workgroup per CU, as run_forward_p2u)
+  if (t.a.x) {
+    if (uniform) k_forward_p2_tiled<P, true, true><<<grid, block, lds_pad, s>>>(t);
+    else k_forward_p2_tiled<P, true, false><<<grid, block, lds_pad, s>>>(t);
+  } else {
+    if (uniform) k_forward_p2_tiled<P, false, true><<<grid, block, lds_pad, s>>>(t);
+    else k_forward_p2_tiled<P, false, false><<<grid, block, lds_pad, s>>>(t);
+  }
+}
+int launch_forward_p2_tiled(const ProblemDesc& p, const GridDesc& g, int nodes, int batch, const double* x0,
+                            const double* u, double* x, double* J, hipStream_t s) {
+  if (!pipeline_supported(p.functor, p.nS, p.nC) || p.pb || g.N < 8 || g.N % 8 != 0 || g.N >= nodes || batch < 1) return -1;
+  // the lane offsets of the buffer stores span the workgroup's tiles: 32 bits, below num_records
+  if (4 * tiled_tile_doubles((size_t)p.nS + 1, (size_t)nodes) * sizeof(double) >= (size_t)kNumRecP2) return -1;
+  const FwdArgsP2Tiled t{FwdArgsP2{g.N, batch, g.REC, p.ps, nullptr, 0u, x0, u, x, J, nullptr, 0, nullptr}, nodes};
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_forward_p2_tiled<decltype(P)>(t, g.uniform, s); })) return -1;
+  return hip_rc(hipGetLastError());
+}
+
 int launch_forward_p2(const ProblemDesc& p, const GridDesc& g, int batch, const double* x0, const double* u,
                       double* x, double* J, const int* frozen, hipStream_t s, bool no_cost_row, const int* gate) {
   if (!pipeline_problem_ok(p) || !pipeline_shape_ok(p.nS, g.N, batch, false)) return -1;

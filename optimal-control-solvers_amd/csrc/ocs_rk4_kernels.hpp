@@ -213,6 +213,158 @@ __global__ __launch_bounds__(64) void k_forward(const FwdArgs a) {
   if (warm == 1.234567e300) a.J[b] = warm;  // never true for a table of step sizes; keeps the sweep alive
 }
 
+// The same pass on tiled x and u (OCS_LAYOUT_TILED; DevLayout, ocs_device_common.hpp): k_forward's walk, with the tiled row
+// stride and trajectory offset, for the plain case (control samples from memory, nothing frozen, cached stores).  It shares the
+// step (lane_state_step) and the record ring with k_forward.  nodes: the columns N + 1 of the WHOLE x array -- a launch that
+// continues another kernel's pass gets pointers to a later column, and a.N counts its own steps.  A lane past the end of the
+// batch is clamped like any other, so pad lanes are neither read nor written.  col0: x0 and yc0 point into a column of the
+// tiled x (the boundary column of a split pass), not at [nS][B] vectors.
+struct FwdArgsTiled {
+  FwdArgs a;
+  int nodes;   // N + 1 of the whole pass
+  int col0;    // x0 / yc0 are a column of the tiled x
+};
+template <class P, int CH, int PF, bool OUT_X>
+__global__ __launch_bounds__(64) void k_forward_tiled(const FwdArgsTiled t) {
+  constexpr bool UCONST = false, NT = false;
+  const FwdArgs& a = t.a;
+  const int nodes = t.nodes;
+  if (a.gate && *a.gate == 0) return;
+  constexpr int NS = P::NS, NC = P::NC, NTC = P::NTC;
+  using Rec = StepRec<NTC>;
+  const int b0 = blockIdx.x * 64 + threadIdx.x;
+  const int b = b0 < a.batch ? b0 : a.batch - 1;
+  const size_t B = (size_t)a.batch;
+  const DevLayout<true> LX = DevLayout<true>::make(B, NS + 1, nodes), LU = DevLayout<true>::make(B, NC, 2 * nodes - 1);
+  const size_t RX = LX.row(), RU = LU.row();   // row strides of x and u (k_forward: B)
+  const size_t V0 = t.col0 ? RX : B, v0 = t.col0 ? LX.at(b) : (size_t)b;   // ... and of x0 / yc0
+  const int N = a.N;
+  const uniform_ptr PS = as_uniform(a.ps);
+  const double* REC = a.REC;
+
+  const typename P::Par p = P::load(ParamSrc{PS, a.pb, a.pmask, B, b});
+
+  const double warm = warm_table(a.REC, (size_t)N * rec_stride(NTC));
+
+  double y[NS], yc = a.yc0 ? a.yc0[v0] : 0.0;  // xK(:,1,1) = [x0; 0]   :33
+#pragma unroll
+  for (int k = 0; k < NS; ++k) y[k] = a.x0[(size_t)k * V0 + v0];
+  // All per-step arrays are walked with one pointer that advances by one row stride (B doubles, batch-minor) per row:
+  // rows of consecutive time points are one stride apart, so no per-row offset arithmetic is needed.
+  // frozen lanes write every row to one scratch double (pointer stride 0): no branch around the stores
+  const bool fz = a.frozen && a.frozen[b] != 0;
+  const size_t xstep = fz ? 0 : RX;
+  double* xo = fz ? a.dump + b : a.x + LX.at(b);
+  if (OUT_X) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      *xo = y[k];
+      xo += xstep;
+    }
+    *xo = yc;
+    xo += xstep;
+  }
+
+  const double* up = a.u;  // walks u(:,j) row by row
+  double uprev[NC];
+  if (UCONST) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) uprev[c] = PSU(a.u)[c];
+  } else {
+    up += LU.at(b);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      uprev[c] = *up;
+      up += RU;
+    }
+  }
+
+  // one RK4 step (lane_state_step, ocs_device_common.hpp) and the stores of its node
+  auto step = [&](const Rec& r, const double* uA, const double* uM, const double* uB) OCS_INLINE {
+    lane_state_step<P>(r, y, yc, uA, uM, uB, p);
+    if (OUT_X) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        OCS_LANE_ST(xo, y[k]);
+        xo += xstep;
+      }
+      OCS_LANE_ST(xo, yc);
+      xo += xstep;
+    }
+  };
+
+  // controls are prefetched one chunk (CH steps = 2*CH samples) ahead, ping-pong in registers;
+  // the uniform step record is fetched one step ahead
+  double ub0[2 * CH][NC], ub1[2 * CH][NC];
+  auto load_chunk = [&](double (&dst)[2 * CH][NC]) OCS_INLINE {
+#pragma unroll
+    for (int s = 0; s < 2 * CH; ++s)
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc) {
+        dst[s][cc] = *up;
+        up += RU;
+      }
+  };
+  Rec rq[PF];  // walks forward one record per step; the table is padded past step N-1
+  const double* recp = REC;
+#pragma unroll
+  for (int q = 0; q < PF; ++q) {
+    rq[q] = load_rec<NTC>(recp);
+    recp += rec_stride(NTC);
+  }
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, 1>(rq, recp); };
+  auto run_chunk = [&](const double (&src)[2 * CH][NC]) OCS_INLINE {
+#pragma unroll
+    for (int s = 0; s < CH; ++s) {
+      const Rec cur = next_rec();
+      const double* uA = (s == 0) ? uprev : src[2 * s - 1];
+      step(cur, uA, src[2 * s], src[2 * s + 1]);
+    }
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) uprev[cc] = src[2 * CH - 1][cc];
+  };
+
+  if (UCONST) {  // constant control (tail leg of RK4InfiniteIntegrator.m:15): nothing to load
+    for (int i = 0; i < N; ++i) {
+      const Rec cur = next_rec();
+      step(cur, uprev, uprev, uprev);
+    }
+    if (!fz) a.J[b] = a.Jadd ? a.Jadd[b] + yc : yc;
+    if (warm == 1.234567e300) a.J[b] = warm;
+    return;
+  }
+  const int nch = N / CH;
+  if (nch > 0) load_chunk(ub0);
+  int c = 0;
+  for (; c + 1 < nch; c += 2) {
+    load_chunk(ub1);
+    run_chunk(ub0);
+    if (c + 2 < nch) load_chunk(ub0);
+    run_chunk(ub1);
+  }
+  if (c < nch) run_chunk(ub0);
+  for (int i = nch * CH; i < N; ++i) {  // remainder steps, direct loads
+    double uM[NC], uB[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) {
+      uM[cc] = *up;
+      up += RU;
+    }
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) {
+      uB[cc] = *up;
+      up += RU;
+    }
+    const Rec cur = next_rec();
+    step(cur, uprev, uM, uB);
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) uprev[cc] = uB[cc];
+  }
+  if (!fz) a.J[b] = a.Jadd ? a.Jadd[b] + yc : yc;  // J = x(end,end)   :55
+  if (warm == 1.234567e300) a.J[b] = warm;  // never true for a table of step sizes; keeps the sweep alive
+}
+
+
 // ---------------------------------------------------------------------------------------
 // adjoint pass: [lam, dJdu] = compute_adjoints(obj, prob, u, lamT)   RK4Integrator.m:59-121
 // ---------------------------------------------------------------------------------------
@@ -433,6 +585,219 @@ __global__ __launch_bounds__(64) void k_backward(const BwdArgs a) {
     if (a.lam0) a.lam0[b] = warm;
   }
 }
+
+// The same pass on tiled checkpoints, u, lam and dJdu (OCS_LAYOUT_TILED): k_backward's walk with the tiled row stride and
+// trajectory offset, for the plain case (samples from memory, all checkpoints read, cached stores); shares lane_adjoint_step and
+// the record ring with k_backward.  nodes: N + 1 of the whole pass, as for k_forward_tiled.
+struct BwdArgsTiled {
+  BwdArgs a;
+  int nodes;   // N + 1 of the whole pass
+};
+template <class P, int CH, int PF, bool OUT_LAM, bool OUT_DJDU>
+__global__ __launch_bounds__(64) void k_backward_tiled(const BwdArgsTiled t) {
+  constexpr bool UCONST = false, XRC = false;
+  const BwdArgs& a = t.a;
+  const int nodes = t.nodes;
+  constexpr bool NT = XRC;   // (the same launches: HBM-bound, outputs larger than the memory-side cache)
+  static_assert(!XRC || (PF >= CH && !UCONST), "re-integration: the record ring must hold a chunk");
+  constexpr int NS = P::NS, NC = P::NC, NTC = P::NTC, NAUG = P::NAUG;
+  using Rec = StepRec<NTC>;
+  const int b0 = blockIdx.x * 64 + threadIdx.x;
+  const int b = b0 < a.batch ? b0 : a.batch - 1;
+  const size_t B = (size_t)a.batch;
+  const DevLayout<true> LX = DevLayout<true>::make(B, NAUG, nodes), LU = DevLayout<true>::make(B, NC, 2 * nodes - 1);
+  const size_t RX = LX.row(), RU = LU.row();   // row strides of x / lam and of u / dJdu (k_backward: B)
+  const int N = a.N;
+  const uniform_ptr PS = as_uniform(a.ps);
+  const double* REC = a.REC;
+
+  const typename P::Par p = P::load(ParamSrc{PS, a.pb, a.pmask, B, b});
+
+  const double warm = warm_table(a.REC, (size_t)N * rec_stride(NTC));
+
+  double lam[NS], lamc;  // lam(:,end) = lamT   :69.  lamc = lam(end,:) is constant: the last row
+  if (a.lamT) {          // of dFdx_times_vec is 0 (OCProblem.m:14-15), adding zeros is exact.
+#pragma unroll
+    for (int k = 0; k < NS; ++k) lam[k] = a.lamT[(size_t)k * B + b];
+    lamc = a.lamT[(size_t)NS * B + b];
+  } else {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) lam[k] = 0.0;
+    lamc = 1.0;
+  }
+  // every array is walked downwards one row (one row stride) at a time, last row of a column first
+  double* lo = a.lam + LX.at(b) + ((size_t)(N + 1) * NAUG) * RX;      // one past lam(end,N+1)
+  const double* up = a.u;
+  if (!UCONST) {
+    up += LU.at(b) + ((size_t)(2 * N + 1) * NC) * RU;  // one past u(end,2N+1)
+  }
+  const double* xp = a.xck + LX.at(b) + ((size_t)N * NAUG) * RX;     // x(1,N+1): one past x(end,N)
+  double* dp = a.dJdu + LU.at(b) + ((size_t)(2 * N + 1) * NC) * RU;     // one past dJdu(end,2N+1)
+  if (OUT_LAM) {
+    lo -= RX;
+    *lo = lamc;
+#pragma unroll
+    for (int k = NS - 1; k >= 0; --k) {
+      lo -= RX;
+      *lo = lam[k];
+    }
+  }
+
+  double unext[NC], pend[NC];  // u(:,2i+3) carried from the step above; k1-term of that step
+#pragma unroll
+  for (int c = NC - 1; c >= 0; --c) {
+    if (UCONST) {
+      unext[c] = PSU(a.u)[c];
+    } else {
+      up -= RU;
+      unext[c] = *up;
+    }
+    pend[c] = 0.0;
+  }
+
+  // reverse of RK4 step i: xi = y_i (checkpoint), controls uA (2i), uM (2i+1), uB (2i+2)
+  auto step = [&](const Rec& r, const double* xi, const double* uA, const double* uM, const double* uB) OCS_INLINE {
+    lane_adjoint_step<P, OUT_DJDU>(r, xi, uA, uM, uB, p, lam, lamc, pend,
+                               [&](const double* dn, const double* dm) OCS_INLINE {
+#pragma unroll
+      for (int c = NC - 1; c >= 0; --c) {
+        dp -= RU;
+        OCS_LANE_ST(dp, dn[c]);  // column 2i+2
+      }
+#pragma unroll
+      for (int c = NC - 1; c >= 0; --c) {
+        dp -= RU;
+        OCS_LANE_ST(dp, dm[c]);  // column 2i+1
+      }
+    });
+    if (OUT_LAM) {
+      lo -= RX;
+      OCS_LANE_ST(lo, lamc);
+#pragma unroll
+      for (int k = NS - 1; k >= 0; --k) {
+        lo -= RX;
+        OCS_LANE_ST(lo, lam[k]);
+      }
+    }
+  };
+
+  const int nch = UCONST ? 0 : N / CH;
+  Rec rq[PF];  // walks down; padded before step 0
+  const double* recp = REC + (size_t)(N - 1) * rec_stride(NTC);
+#pragma unroll
+  for (int q = 0; q < PF; ++q) {
+    rq[q] = load_rec<NTC>(recp);
+    recp -= rec_stride(NTC);
+  }
+  auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, -1>(rq, recp); };
+  // remainder steps at the top of the grid first (i = N-1 .. nch*CH), direct loads
+  for (int i = N - 1; i >= nch * CH; --i) {
+    double xi[NS], uA[NC], uM[NC];
+    xp -= RX;  // skip the cost row: y(end) is never read (OCProblem.m:14-15)
+#pragma unroll
+    for (int k = NS - 1; k >= 0; --k) {
+      xp -= RX;
+      xi[k] = *xp;
+    }
+    if (UCONST) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) uA[c] = uM[c] = unext[c];
+    } else {
+#pragma unroll
+      for (int c = NC - 1; c >= 0; --c) {
+        up -= RU;
+        uM[c] = *up;
+      }
+#pragma unroll
+      for (int c = NC - 1; c >= 0; --c) {
+        up -= RU;
+        uA[c] = *up;
+      }
+    }
+    const Rec cur = next_rec();
+    step(cur, xi, uA, uM, unext);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) unext[c] = uA[c];
+  }
+
+  // a chunk covers CH steps: checkpoints x(:,i) and the 2*CH samples below the carried one
+  double xb0[CH][NS], xb1[CH][NS], ub0[2 * CH][NC], ub1[2 * CH][NC];
+  auto load_chunk = [&](double (&xd)[CH][NS], double (&ud)[2 * CH][NC]) OCS_INLINE {
+#pragma unroll
+    for (int s = CH - 1; s >= 0; --s) {
+      if (XRC && s > 0) {   // integrated from checkpoint 0 of the chunk in run_chunk
+        xp -= (size_t)(NS + 1) * RX;
+        continue;
+      }
+      xp -= RX;  // cost row skipped
+#pragma unroll
+      for (int k = NS - 1; k >= 0; --k) {
+        xp -= RX;
+        xd[s][k] = *xp;
+      }
+    }
+#pragma unroll
+    for (int s = 2 * CH - 1; s >= 0; --s)
+#pragma unroll
+      for (int cc = NC - 1; cc >= 0; --cc) {
+        up -= RU;
+        ud[s][cc] = *up;
+      }
+  };
+  auto run_chunk = [&](const double (&xs0)[CH][NS], const double (&us)[2 * CH][NC]) OCS_INLINE {
+    double xs[CH][NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) xs[0][k] = xs0[0][k];
+#pragma unroll
+    for (int s = 1; s < CH; ++s) {
+      if (XRC) {   // x(:, i0 + s) from x(:, i0 + s - 1): compute_states :39-51 on the state rows, the state pass's operations
+        // the ring holds the records of steps i0 + CH - 1 (rq[0]) .. i0 (rq[CH - 1])
+#pragma unroll
+        for (int k = 0; k < NS; ++k) xs[s][k] = xs[s - 1][k];
+        lane_state_rows_step<P>(rq[CH - s], xs[s], us[2 * s - 2], us[2 * s - 1], us[2 * s], p);
+      } else {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) xs[s][k] = xs0[s][k];
+      }
+    }
+#pragma unroll
+    for (int s = CH - 1; s >= 0; --s) {
+      const Rec cur = next_rec();
+      const double* uB = (s == CH - 1) ? unext : us[2 * s + 2];
+      step(cur, xs[s], us[2 * s], us[2 * s + 1], uB);
+    }
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) unext[cc] = us[0][cc];
+  };
+  int c = nch - 1;
+  if (c >= 0) load_chunk(xb0, ub0);
+  for (; c >= 1; c -= 2) {
+    load_chunk(xb1, ub1);
+    run_chunk(xb0, ub0);
+    if (c >= 2) load_chunk(xb0, ub0);
+    run_chunk(xb1, ub1);
+  }
+  if (c == 0) run_chunk(xb0, ub0);
+
+  if (OUT_DJDU) {
+#pragma unroll
+    for (int cc = NC - 1; cc >= 0; --cc) {
+      dp -= RU;
+      *dp = pend[cc];  // left end point :101-102
+    }
+  }
+  if (a.lam0) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) a.lam0[(size_t)k * B + b] = lam[k];
+    a.lam0[(size_t)NS * B + b] = lamc;
+  }
+  if (warm == 1.234567e300) {  // never true; keeps the table sweep alive
+    if (OUT_DJDU) *dp = warm;
+    if (OUT_LAM) *lo = warm;
+    if (a.lam0) a.lam0[b] = warm;
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------
 // plugin methods for k columns (used by the API's ocs_problem_F & friends)

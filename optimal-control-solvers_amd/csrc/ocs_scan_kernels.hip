@@ -177,6 +177,40 @@ int launch_costate_scan_met(const ProblemDesc& p, const GridDesc& g, int batch, 
 }
 
 int scan_chunk_steps() { return kScanL; }
+// the same pass on tiled arrays: g.N whole chunks of a pass of `nodes` - 1 steps; lamT_col: lamT is a column of the tiled lam
+template <class P>
+static void run_backward_scan_tiled(const BwdArgsScanTiled& t, hipStream_t s) {
+  constexpr int TPW = 64 / P::NS;
+  const BwdArgsScan& a = t.a;
+  const dim3 grid((a.batch + TPW - 1) / TPW), block(kScanW * 64);
+  if (a.lamT) {
+    if (a.lam && a.dJdu)
+      k_backward_scan_tiled<P, kScanW, kScanL, true, true, true><<<grid, block, 0, s>>>(t);
+    else if (a.lam)
+      k_backward_scan_tiled<P, kScanW, kScanL, true, false, true><<<grid, block, 0, s>>>(t);
+    else
+      k_backward_scan_tiled<P, kScanW, kScanL, false, true, true><<<grid, block, 0, s>>>(t);
+  } else if (a.lam && a.dJdu) {
+    k_backward_scan_tiled<P, kScanW, kScanL, true, true, false><<<grid, block, 0, s>>>(t);
+  } else if (a.lam) {
+    k_backward_scan_tiled<P, kScanW, kScanL, true, false, false><<<grid, block, 0, s>>>(t);
+  } else {
+    k_backward_scan_tiled<P, kScanW, kScanL, false, true, false><<<grid, block, 0, s>>>(t);
+  }
+}
+int launch_backward_scan_tiled(const ProblemDesc& p, const GridDesc& g, int nodes, int batch, const double* xck,
+                               const double* u, const double* lamT, bool lamT_col, double* lam, double* dJdu, double* lam0,
+                               const double* pend0, hipStream_t s) {
+  if (!scan_supported(p.functor, p.nS, p.nC) || p.pb || (!lam && !dJdu) || g.N < kScanL || g.N % kScanL != 0 ||
+      g.N >= nodes || batch < 1 || !g.RECS)
+    return -1;
+  // the lane offsets of the buffer accesses span the workgroup's tiles: 32 bits, below num_records
+  if (4 * tiled_tile_doubles((size_t)p.nS + 1, (size_t)nodes) * sizeof(double) >= (size_t)kNumRec) return -1;
+  const BwdArgsScanTiled t{BwdArgsScan{g.N, batch, g.RECS, p.ps, nullptr, 0u, xck, u, lamT, lam, dJdu, lam0, pend0}, nodes,
+                           lamT_col ? 1 : 0};
+  if (!for_logistic<1, 2, 4>(p.nS, [&](auto P) { run_backward_scan_tiled<decltype(P)>(t, s); })) return -1;
+  return hip_rc(hipGetLastError());
+}
 int launch_backward_scan(const ProblemDesc& p, const GridDesc& g, int batch, const double* xck, const double* u,
                          const double* lamT, double* lam, double* dJdu, double* lam0, const double* pend0,
                          hipStream_t s) {

@@ -32,6 +32,7 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
                                   int nFree, const int* FreeInitStates, const double* Lb, const double* Ub,
                                   const ocs_ss_options* opt, double* J, int* iterations, int* converged,
                                   double* pgnorm, void* stream) {
+  OCS_TRY(refuse_tiled(g, "ocs_single_shooting"));
   OCS_TRACE("ocs_single_shooting_batch_dev");
   if (!g || !p || !c || !x0 || !v || !opt || !J || batch < 1 || nFree < 0) return fail(OCS_ERR_INVALID, "bad argument");
   if (opt->MaxIter < 0 || opt->memory < 1 || opt->maxBacktracks < 1 || !(opt->TolFun > 0))

@@ -26,6 +26,45 @@ def _dptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+# ---- the tiled device layout (include/ocs.h, ocs_integrator_set_layout) ----------------------
+TILE = 16
+
+
+def tiled_doubles(rows, cols, batch):
+    """doubles of a tiled array of `cols` columns x `rows` rows x `batch` trajectories (whole tiles of 16)"""
+    return int(check(lib.ocs_tiled_doubles(rows, cols, batch)))
+
+
+def tiled_index(rows, cols, batch):
+    """The index map of the tiled layout, in NumPy: an int64 array [cols][rows][batch] whose entry (i, r, b) is the
+    position of that element in the flat tiled array, ((b // 16) * cols + i) * rows * 16 + r * 16 + b % 16."""
+    i = np.arange(cols, dtype=np.int64)[:, None, None]
+    r = np.arange(rows, dtype=np.int64)[None, :, None]
+    b = np.arange(batch, dtype=np.int64)[None, None, :]
+    return ((b // TILE) * cols + i) * rows * TILE + r * TILE + b % TILE
+
+
+def to_tiled(src, out=None):
+    """batch-minor device tensor [cols][rows][B] -> flat tiled tensor (pad lanes: copies of the last trajectory)"""
+    cols, rows, B = src.shape
+    assert src.is_cuda and src.dtype == torch.float64 and src.is_contiguous()
+    if out is None:
+        out = torch.empty(tiled_doubles(rows, cols, B), dtype=torch.float64, device=src.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == tiled_doubles(rows, cols, B)
+    check(lib.ocs_to_tiled_dev(_dptr(src), _dptr(out), rows, cols, B, _stream()))
+    return out
+
+
+def from_tiled(src, rows, cols, batch, out=None):
+    """flat tiled device tensor -> batch-minor [cols][rows][batch]"""
+    assert src.is_cuda and src.dtype == torch.float64 and src.is_contiguous() and src.numel() == tiled_doubles(rows, cols, batch)
+    if out is None:
+        out = torch.empty((cols, rows, batch), dtype=torch.float64, device=src.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (cols, rows, batch)
+    check(lib.ocs_from_tiled_dev(_dptr(src), _dptr(out), rows, cols, batch, _stream()))
+    return out
+
+
 class Integrator:
     """Integrator/Integrator.m:6-15: property t, compute_states, compute_adjoints."""
     t = None
@@ -56,6 +95,7 @@ class RK4Integrator(Integrator):
         check(lib.ocs_integrator_t(h, _p(self.t)))
         check(lib.ocs_integrator_h(h, _p(self.h)))
         self._batch_shape = None
+        self._layout = "batch_minor"
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -68,6 +108,18 @@ class RK4Integrator(Integrator):
         code = mapping if isinstance(mapping, int) else {"auto": 0, "lane": 1, "rowsplit": 2, "pipeline": 3, "scan": 4}[mapping]
         check(lib.ocs_integrator_set_mapping(self._h, code))
         return self
+
+    def set_layout(self, layout):
+        """Device layout of the per-step arrays of compute_states_dev / compute_adjoints_dev: "batch_minor" (default,
+        [cols][rows][B]) or "tiled" (flat tensors of tiled_doubles(rows, cols, B) doubles; see to_tiled / from_tiled)."""
+        code = layout if isinstance(layout, int) else {"batch_minor": 0, "tiled": 1}[layout]
+        check(lib.ocs_integrator_set_layout(self._h, code))
+        self._layout = "tiled" if code == 1 else "batch_minor"
+        return self
+
+    @property
+    def layout(self):
+        return self._layout
 
     # ---- host path (MATLAB shapes) -------------------------------------------------
     def compute_states(self, prob, x0, u):
@@ -102,11 +154,14 @@ class RK4Integrator(Integrator):
 
     # ---- device path (batch-minor torch tensors, async on the current stream) --------
     @staticmethod
-    def _chk(name, t, shape, dev):
+    def _chk(name, t, shape, dev, tiled=False):
         """a wrongly sized or misplaced device tensor is an out-of-bounds access inside a kernel, i.e. a GPU fault:
-        check shape, dtype, contiguity and device here"""
+        check shape, dtype, contiguity and device here.  tiled: the per-step array [cols][rows][B] named by `shape` is
+        held in the tiled layout, a flat tensor of whole tiles"""
         if t is None:
             return
+        if tiled:
+            shape = (tiled_doubles(shape[1], shape[0], shape[2]),)
         if tuple(t.shape) != tuple(shape) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"{name}: expected a contiguous float64 tensor of shape {tuple(shape)} on {dev}, "
                              f"got {tuple(t.shape)} {t.dtype} on {t.device}")
@@ -119,22 +174,25 @@ class RK4Integrator(Integrator):
         if J is None:
             J = torch.empty(B, dtype=torch.float64, device=dev)
         self._chk("x0", x0, (nS, B), dev)
-        self._chk("u", u, (2 * N + 1, nC, B), dev)
-        self._chk("x", x, (N + 1, nS + 1, B), dev)
+        tl = self._layout == "tiled"
+        self._chk("u", u, (2 * N + 1, nC, B), dev, tiled=tl)
+        self._chk("x", x, (N + 1, nS + 1, B), dev, tiled=tl)
         self._chk("J", J, (B,), dev)
         check(lib.ocs_compute_states_dev(self._h, prob._h, B, _dptr(x0), _dptr(u), _dptr(x), _dptr(J),
                                          _stream()))
         self._ck_ref = x   # the adjoint pass re-reads it (the xK contract): keep it alive until then
         return x, J
 
-    def compute_adjoints_dev(self, prob, u, lamT=None, lam=None, dJdu=None):
+    def compute_adjoints_dev(self, prob, u, lamT=None, lam=None, dJdu=None, batch=None):
+        """batch: needed on a handle set to the tiled layout, whose flat u does not tell it"""
         N = self.nSTEPS
-        B = u.shape[-1]
+        B = u.shape[-1] if batch is None else batch
         nS, nC, dev = prob.nS, prob.ControlBounds.shape[0], u.device
-        self._chk("u", u, (2 * N + 1, nC, B), dev)
+        tl = self._layout == "tiled"
+        self._chk("u", u, (2 * N + 1, nC, B), dev, tiled=tl)
         self._chk("lamT", lamT, (nS + 1, B), dev)
-        self._chk("lam", lam, (N + 1, nS + 1, B), dev)
-        self._chk("dJdu", dJdu, (2 * N + 1, nC, B), dev)
+        self._chk("lam", lam, (N + 1, nS + 1, B), dev, tiled=tl)
+        self._chk("dJdu", dJdu, (2 * N + 1, nC, B), dev, tiled=tl)
         check(lib.ocs_compute_adjoints_dev(self._h, prob._h, B, _dptr(u), _dptr(lamT), _dptr(lam),
                                            _dptr(dJdu), _stream()))
         return lam, dJdu

@@ -1,4 +1,5 @@
-"""Steady-state loop timings: K forwards back to back, K adjoints back to back, K pairs (MAPPING=auto|pipeline|scan|lane).
+"""Steady-state loop timings: K forwards back to back, K adjoints back to back, K pairs (MAPPING=auto|pipeline|scan|lane;
+LAYOUT=batch_minor|tiled: the arrays are tiled, ocs_integrator_set_layout).
 The pair is what bench.py times; the difference to the sum of the two
 single-kernel loops is the interference between the kernels (cache write-back, clocks)."""
 import os, sys, time, numpy as np, torch
@@ -15,14 +16,18 @@ integ = ocs.RK4Integrator(tspan).set_mapping(os.environ.get('MAPPING', 'auto'))
 x0 = torch.ones((nS, batch), dtype=torch.float64, device=dev)
 u = 0.05 + 0.4 * torch.rand((2 * N + 1, 1, batch), dtype=torch.float64, device=dev)
 x = torch.empty((N + 1, nS + 1, batch), dtype=torch.float64, device=dev)
+tiled = os.environ.get('LAYOUT', 'batch_minor') == 'tiled'
+kw = {'batch': batch} if tiled else {}
+if tiled:
+    integ.set_layout('tiled'); u, x = ocs.to_tiled(u), ocs.to_tiled(x)
 lam = torch.empty_like(x); d = torch.empty_like(u)
 def loop(what, K=50):
     for _ in range(5):
-        integ.compute_states_dev(prob, x0, u, x); integ.compute_adjoints_dev(prob, u, None, lam, d)
+        integ.compute_states_dev(prob, x0, u, x); integ.compute_adjoints_dev(prob, u, None, lam, d, **kw)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(K):
         if 'f' in what: integ.compute_states_dev(prob, x0, u, x)
-        if 'b' in what: integ.compute_adjoints_dev(prob, u, None, lam, d)
+        if 'b' in what: integ.compute_adjoints_dev(prob, u, None, lam, d, **kw)
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / K * 1e6
 for what in ('f', 'b', 'fb', 'f', 'b', 'fb'):
     print(what, f"{loop(what):.1f} us per iteration", flush=True)
