@@ -222,6 +222,21 @@ int ocs_compute_adjoints_dev(ocs_integrator g, ocs_problem p, int batch, const d
  * lam2(:,1) of the tail leg under the constant control uStar); lamT must be NULL. */
 int ocs_rk4inf_create(ocs_integrator *out, const double *tspan, int npts, const double *tspanExtra,
                       int nptsExtra, const double *uStar, int nC);
+/* A constant tail control of its own per trajectory (batch extension: no counterpart in the reference, which integrates one
+ * trajectory per call).  Per trajectory b the results of compute_states / compute_adjoints and of everything built on them
+ * (ocs_nlp_objective*, ocs_single_shooting_batch*) equal those of RK4InfiniteIntegrator(tspan, tspanExtra, uStar(:,b)) --
+ * e.g. the uStar of each instance's own ocs_compute_equilibrium, under per-trajectory problem parameters or LQ weights.
+ * host: uStar nC x batch, column-major (nC as given to ocs_rk4inf_create).  batch == 0 or uStar == NULL clears it: the
+ * handle is back to the shared uStar of ocs_rk4inf_create, bit for bit.
+ * _dev: uStar is a device array, batch-minor [nC][batch]; it is COPIED on `stream` into a buffer the handle owns (the
+ * caller's array is not borrowed and may be reused once the copy has run).
+ * OCS_ERR_INVALID: null handle or an RK4Integrator handle; OCS_ERR_SHAPE: batch < 0.  While it is set, a compute call with
+ * another batch (or a problem with another nC) fails with OCS_ERR_SHAPE, as for per-trajectory parameters.  A set or clear
+ * between compute_states and compute_adjoints makes the latter fail with OCS_ERR_ORDER.  Every mapping the tail leg takes
+ * reads it (lane kernels, hipRTC plugins, the wave-specialised tail, the LQ matrix-core kernels and their chunked tail).
+ * ocs_multi_*: set block [lo, hi) of ocs_multi_shard on device k's own integrator handle. */
+int ocs_rk4inf_set_batch_ustar(ocs_integrator g, int batch, const double *uStar);
+int ocs_rk4inf_set_batch_ustar_dev(ocs_integrator g, int batch, const double *uStar, void *stream);
 
 /* ---- Control (Control/Control.m:4-14 and PWLinearControl.m / PWConstantControl.m / ChebyshevControl.m) ----
  * v is a column with the control index fastest: v(c + nC*(i-1)), i = basis function. */

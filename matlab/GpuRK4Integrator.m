@@ -13,14 +13,22 @@ classdef GpuRK4Integrator < Integrator
          obj.hnd = libpointer('voidPtrPtr');
          if nargin == 1
             ocs_check(calllib('libocs', 'ocs_rk4_create', obj.hnd, tspan, numel(tspan)));
-         else
+         elseif isvector(uStar)                 % the reference's uStar: nC values shared by every trajectory
             ocs_check(calllib('libocs', 'ocs_rk4inf_create', obj.hnd, tspan, numel(tspan), ...
                               tspanExtra, numel(tspanExtra), uStar, numel(uStar)));
+         else                                   % nC x B: a uStar per trajectory (batch extension, no counterpart in the reference)
+            ocs_check(calllib('libocs', 'ocs_rk4inf_create', obj.hnd, tspan, numel(tspan), ...
+                              tspanExtra, numel(tspanExtra), uStar(:, 1), size(uStar, 1)));
+            obj.set_batch_uStar(uStar);
          end
          obj.nSTEPS = numel(tspan) - 1;
          obj.t = zeros(1, 2*obj.nSTEPS + 1);  obj.h = zeros(1, obj.nSTEPS);
          [~, ~, obj.t] = calllib('libocs', 'ocs_integrator_t', obj.hnd.Value, obj.t);
          [~, ~, obj.h] = calllib('libocs', 'ocs_integrator_h', obj.hnd.Value, obj.h);
+      end
+      function set_batch_uStar(obj, uStar)      % uStar nC x B: trajectory b runs as RK4InfiniteIntegrator(tspan, tspanExtra, uStar(:,b));
+         if nargin < 2, uStar = []; end         % no argument / []: back to the shared uStar of the constructor
+         ocs_check(calllib('libocs', 'ocs_rk4inf_set_batch_ustar', obj.hnd.Value, size(uStar, 2), uStar));
       end
       function [x, J] = compute_states(obj, prob, x0, u)          % RK4Integrator.m:28
          batch = size(u, 3);

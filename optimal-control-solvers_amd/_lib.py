@@ -74,6 +74,8 @@ _SIG = {
     "ocs_compute_states_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "ocs_compute_adjoints_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "ocs_rk4inf_create": (C.c_int, [C.POINTER(vp), dp, C.c_int, dp, C.c_int, dp, C.c_int]),
+    "ocs_rk4inf_set_batch_ustar": (C.c_int, [vp, C.c_int, dp]),
+    "ocs_rk4inf_set_batch_ustar_dev": (C.c_int, [vp, C.c_int, vp, vp]),
     "ocs_control_create": (C.c_int, [C.POINTER(vp), C.c_int, dp, C.c_int, C.c_int, C.c_int]),
     "ocs_control_destroy": (C.c_int, [vp]),
     "ocs_control_dims": (C.c_int, [vp, ip, ip, ip]),

@@ -280,6 +280,54 @@ int ocs_rk4inf_create(ocs_integrator* out, const double* tspan, int npts, const 
   return OCS_OK;
 }
 
+// which uStar the tail leg of (g, batch) runs under; refuses a batch other than the per-trajectory uStar's
+static int tail_ustar(const ocs_integrator_s* g, int batch, const double** u, bool* per_traj) {
+  if (g->ustar_batch && g->ustar_batch != batch)
+    return fail(OCS_ERR_SHAPE, "integrator has a per-trajectory uStar for batch %d, call has batch %d", g->ustar_batch, batch);
+  *per_traj = g->ustar_batch != 0;
+  *u = *per_traj ? g->d_ustar_b.d() : g->d_ustar.d();
+  return OCS_OK;
+}
+static int batch_ustar_check(ocs_integrator g, int batch) {
+  if (!g) return fail(OCS_ERR_INVALID, "null integrator");
+  if (g->kind != 1) return fail(OCS_ERR_INVALID, "a per-trajectory uStar needs an RK4InfiniteIntegrator");
+  if (batch < 0) return fail(OCS_ERR_SHAPE, "batch must be >= 0");
+  return OCS_OK;
+}
+// every set and clear: a new version, and the checkpoints of a state pass under the earlier uStar no longer serve an adjoint pass
+static void batch_ustar_changed(ocs_integrator g) {
+  g->ustar_batch = 0;
+  g->ustar_version = next_version();
+  g->ck = nullptr;
+  g->leg2->ck = nullptr;
+}
+static int batch_ustar_clear(ocs_integrator g) {
+  batch_ustar_changed(g);
+  return OCS_OK;
+}
+int ocs_rk4inf_set_batch_ustar_dev(ocs_integrator g, int batch, const double* uStar, void* stream) {
+  OCS_TRY(batch_ustar_check(g, batch));
+  if (batch == 0 || !uStar) return batch_ustar_clear(g);
+  OCS_TRY(upload_grid(g));
+  const size_t bytes = sizeof(double) * g->ustar.size() * (size_t)batch;
+  batch_ustar_changed(g);   // (and not set if the copy below fails)
+  OCS_TRY(g->d_ustar_b.ensure(bytes));
+  HIP_TRY(hipMemcpyAsync(g->d_ustar_b.p, uStar, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  g->ustar_batch = batch;
+  return OCS_OK;
+}
+int ocs_rk4inf_set_batch_ustar(ocs_integrator g, int batch, const double* uStar) {
+  OCS_TRY(batch_ustar_check(g, batch));
+  if (batch == 0 || !uStar) return batch_ustar_clear(g);
+  OCS_TRY(upload_grid(g));
+  batch_ustar_changed(g);
+  HIP_TRY(hipStreamSynchronize(g->stream));   // (the stage buffer may be in use by a host call's copies)
+  OCS_TRY(stage_in(g->d_stage, g->d_ustar_b, uStar, (int)g->ustar.size(), batch, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));   // complete before a _dev call on any other stream
+  g->ustar_batch = batch;
+  return OCS_OK;
+}
+
 int ocs_integrator_destroy(ocs_integrator g) {
   delete g;   // (~ocs_integrator_s: event, tail leg, sweep and LQ workspaces, stream, then the buffers)
   return OCS_OK;
@@ -366,6 +414,10 @@ int ocs_compute_states_dev(ocs_integrator g, ocs_problem p, int batch, const dou
   // RK4InfiniteIntegrator.m:20-24: [x,J1] = leg1(x0,u); [~,J2] = leg2(x(1:end-1,end), uStar); J = J1 + J2
   if ((int)g->ustar.size() != p->nC) return fail(OCS_ERR_SHAPE, "uStar has %d entries, problem has nC=%d",
                                                  (int)g->ustar.size(), p->nC);
+  const double* us = nullptr;
+  bool us_batch = false;
+  OCS_TRY(upload_grid(g));   // (d_ustar exists from here on)
+  OCS_TRY(tail_ustar(g, batch, &us, &us_batch));
   OCS_TRY(leg_forward(g, p, batch, x0, u, x, J, FwdOpts(), s));
   const double* xT = g->ck + (size_t)g->N * (p->nS + 1) * batch;  // x(1:nS, end): rows are contiguous [nS][B]
   ocs_integrator_s* g2 = g->leg2;
@@ -378,9 +430,10 @@ int ocs_compute_states_dev(ocs_integrator g, ocs_problem p, int batch, const dou
   if (g2->tail_wave) {
     const size_t nU = (size_t)(2 * g2->N + 1) * p->nC * batch;
     OCS_TRY(g2->d_utail.ensure(sizeof(double) * nU));
-    if (g2->utail_batch != batch) {
-      LAUNCH_TRY(launch_fill_rows(2 * g2->N + 1, p->nC, batch, g->d_ustar.d(), g2->d_utail.d(), s));
+    if (g2->utail_batch != batch || g2->utail_version != g->ustar_version) {
+      LAUNCH_TRY(launch_fill_rows(2 * g2->N + 1, p->nC, batch, us, g2->d_utail.d(), s, us_batch));
       g2->utail_batch = batch;
+      g2->utail_version = g->ustar_version;
     }
     OCS_TRY(g2->d_J2.ensure(sizeof(double) * (size_t)batch));
     OCS_TRY(leg_forward(g2, p, batch, xT, g2->d_utail.d(), g2->d_ck.d(), g2->d_J2.d(), FwdOpts(), s));
@@ -389,8 +442,10 @@ int ocs_compute_states_dev(ocs_integrator g, ocs_problem p, int batch, const dou
   }
   FwdOpts o2;
   o2.uconst = true;
+  o2.uconst_batch = us_batch;
+  o2.uversion = g->ustar_version;
   o2.Jadd = J;
-  OCS_TRY(leg_forward(g2, p, batch, xT, g->d_ustar.d(), g2->d_ck.d(), J, o2, s));
+  OCS_TRY(leg_forward(g2, p, batch, xT, us, g2->d_ck.d(), J, o2, s));
   return OCS_OK;
 }
 
@@ -420,7 +475,10 @@ int ocs_compute_adjoints_dev(ocs_integrator g, ocs_problem p, int batch, const d
       return fail(OCS_ERR_ORDER, "tail leg has no forward pass");
     OCS_TRY(bind_problem(g2, p, batch, s));
     OCS_TRY(g->d_lam2.ensure(sizeof(double) * (size_t)(p->nS + 1) * batch));
-    if (g2->tail_wave && g2->utail_batch == batch) {   // (the state pass of the tail ran on the sampled control: so does this)
+    const double* us = nullptr;
+    bool us_batch = false;
+    OCS_TRY(tail_ustar(g, batch, &us, &us_batch));
+    if (g2->tail_wave && g2->utail_batch == batch && g2->utail_version == g->ustar_version) {   // (the state pass of the tail ran on the sampled control: so does this)
       OCS_TRY(g2->d_lamtail.ensure(sizeof(double) * (size_t)(g2->N + 1) * (p->nS + 1) * batch));
       BwdOpts o2;
       o2.mapping = g2->mapping;
@@ -431,8 +489,9 @@ int ocs_compute_adjoints_dev(ocs_integrator g, ocs_problem p, int batch, const d
       BwdOpts o2;
       o2.mapping = g2->mapping;
       o2.uconst = true;
+      o2.uconst_batch = us_batch;
       o2.lam0 = g->d_lam2.d();
-      LAUNCH_TRY(launch_backward(describe(p), describe(g2), batch, g2->ck, g->d_ustar.d(), nullptr, nullptr, nullptr,
+      LAUNCH_TRY(launch_backward(describe(p), describe(g2), batch, g2->ck, us, nullptr, nullptr, nullptr,
                                  o2, s));
       lamT = g->d_lam2.d();
     }

@@ -193,8 +193,17 @@ int launch_add_vec(int n, const double* a, const double* b, double* out, hipStre
   k_add_vec<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(n, a, b, out);
   return hip_rc(hipGetLastError());
 }
-int launch_fill_rows(int ncols, int nC, int batch, const double* val, double* out, hipStream_t s) {
-  k_fill_rows<<<dim3((batch + 255) / 256, ncols), dim3(256), 0, s>>>(ncols, nC, batch, val, out);
+// out[j][c][b] = val[c][b]: samples of a control that is constant in time, one value per trajectory (the tail leg of
+// RK4InfiniteIntegrator under ocs_rk4inf_set_batch_ustar)
+__global__ void k_fill_rows_batch(int ncols, int nC, int batch, const double* __restrict__ val, double* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y;
+  if (b >= batch || j >= ncols) return;
+  for (int c = 0; c < nC; ++c) out[((size_t)j * nC + c) * batch + b] = val[(size_t)c * batch + b];
+}
+int launch_fill_rows(int ncols, int nC, int batch, const double* val, double* out, hipStream_t s, bool per_traj) {
+  if (per_traj) k_fill_rows_batch<<<dim3((batch + 255) / 256, ncols), dim3(256), 0, s>>>(ncols, nC, batch, val, out);
+  else k_fill_rows<<<dim3((batch + 255) / 256, ncols), dim3(256), 0, s>>>(ncols, nC, batch, val, out);
   return hip_rc(hipGetLastError());
 }
 

@@ -212,10 +212,17 @@ struct ocs_integrator_s {
   ocs_integrator_s* leg2 = nullptr;   // integrator2 of RK4InfiniteIntegrator.m:13-14
   std::vector<double> ustar;          // uStar (nC)
   DevBuf d_ustar, d_lam2;             // device uStar [nC]; lam2(:,1) [nAug][B]
+  // a uStar of its own per trajectory (ocs_rk4inf_set_batch_ustar): [nC][ustar_batch], handle-owned; ustar_batch == 0: not
+  // set, the tail leg runs under the shared d_ustar.  ustar_version bumps at every set and clear: what is cached per uStar
+  // (d_utail below, the chunk responses of the LQ tail) is keyed on it, the buffer's address says nothing
+  DevBuf d_ustar_b;
+  int ustar_batch = 0;
+  unsigned long long ustar_version = 0;
   // tail leg of RK4InfiniteIntegrator on the wave-specialised kernels (small batches): the constant control as samples
   // [2N+1][nC][B], the tail's lam [N+1][nAug][B] (its first column is the main leg's lamT), the tail's objective [B]
   DevBuf d_utail, d_lamtail, d_J2;
   int utail_batch = 0;
+  unsigned long long utail_version = 0;   // ustar_version of the main leg the samples were filled under
   bool tail_wave = false;
   int N = 0;
   std::vector<double> tspan, t, h;

@@ -170,6 +170,8 @@ int launch_eval_lq(const ProblemDesc& p, int which, int k, const double* t, cons
 struct FwdOpts {
   int mapping = MAP_AUTO;
   bool uconst = false;          // u is a device [nC] vector shared by all grid points and trajectories
+  bool uconst_batch = false;    // with uconst: u is [nC][B], one constant control per trajectory (ocs_rk4inf_set_batch_ustar)
+  unsigned long long uversion = 0;  // with uconst: bumps whenever the values behind u change (what is cached per u follows it)
   const double* Jadd = nullptr; // J = Jadd + x(end,end)
   const int* frozen = nullptr;  // [B]: trajectories with frozen[b] != 0 store nothing (fb_sweep: converged instances)
   double* dump = nullptr;       // [B] scratch the stores of frozen trajectories go to
@@ -182,6 +184,7 @@ struct FwdOpts {
 struct BwdOpts {
   int mapping = MAP_AUTO;
   bool uconst = false;
+  bool uconst_batch = false;    // as FwdOpts
   double* lam0 = nullptr;       // [nAug][B]: lam(:,1)
   double* split_scratch = nullptr;  // [nAug][B]: hand-over column of a split pass when no lam array is requested
   int layout = LAYOUT_BATCH_MINOR;  // of xck, u, lam and dJdu; tiled: plain passes only, scan + lane remainder
@@ -216,7 +219,8 @@ int launch_basis_contract(int nBasis, int nC, int batch, const int* rowptr, cons
 bool basis_dense_supported(int nBasis);
 int launch_basis_dense(bool expand, int nBasis, int nT, int nC, int batch, const double* BT, const double* in,
                        double* out, hipStream_t s);
-int launch_fill_rows(int ncols, int nC, int batch, const double* val, double* out, hipStream_t s);
+// out[j][c][b] = val[c], or val[c][b] with per_traj (val is [nC][batch])
+int launch_fill_rows(int ncols, int nC, int batch, const double* val, double* out, hipStream_t s, bool per_traj = false);
 // out[i] = a[i] + b[i]
 int launch_add_vec(int n, const double* a, const double* b, double* out, hipStream_t s);
 // RK4InfiniteIntegrator's tail leg (constant control): true where the wave-specialised state pass would be chosen for this grid

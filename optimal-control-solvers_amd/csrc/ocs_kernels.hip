@@ -326,6 +326,7 @@ int launch_forward(const ProblemDesc& p, const GridDesc& g, int batch, const dou
   if (o.uconst && !x) return -1;
   FwdArgs a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, x0, u, x, J, o.Jadd, o.frozen, o.dump, nullptr};
   a.gate = o.gate;
+  a.ub = o.uconst && o.uconst_batch ? batch : 0;
   if (p.functor == Functor::User) {
     void* args[] = {(void*)&a};
     const int kid = o.uconst ? UK_FWD_UCONST : (x ? UK_FWD_X : UK_FWD_J);
@@ -424,7 +425,8 @@ int launch_backward(const ProblemDesc& p, const GridDesc& g, int batch, const do
     return launch_backward_rs(p, g, batch, xck, u, lamT, lam, dJdu, o.lam0, s);
   }
   if (o.uconst ? (lam || dJdu || !o.lam0) : (!lam && !dJdu)) return -1;
-  const BwdArgs a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, xck, u, lamT, lam, dJdu, o.lam0};
+  const BwdArgs a{g.N, batch, g.REC, p.ps, p.pb, p.pmask, xck, u, lamT, lam, dJdu, o.lam0,
+                  o.uconst && o.uconst_batch ? batch : 0};
   if (p.functor == Functor::User) {
     void* args[] = {(void*)&a};
     int kid = o.uconst ? UK_BWD_UCONST : (lam && dJdu ? UK_BWD_LAM_DJDU : (lam ? UK_BWD_LAM : UK_BWD_DJDU));

@@ -26,7 +26,7 @@ struct LQArgs {
   const double* ps;     // [r | A nS x nS col-major | Bu nS x nC | q nS | rdiag nC]
   const double* x0;     // forward: [nS][B]
   const double* xck;    // backward: checkpoints [N+1][nAug][B]
-  const double* u;      // [2N+1][nC][B]; UCONST: [nC]
+  const double* u;      // [2N+1][nC][B]; UCONST: [nC], or [nC][B] with `ub`
   double* x;            // forward out [N+1][nAug][B] or null
   double* J;            // forward out [B]
   const double* Jadd;   // optional [B]
@@ -45,7 +45,14 @@ struct LQArgs {
   // per-trajectory cost weights (ocs_problem_set_batch_params on the weight range; read by the PW instantiations of the
   // integrator passes only): [nS + nC][B], rows 0 .. nS-1 = q, rows nS .. nS+nC-1 = rdiag; null: the shared block's
   const double* W;
+  // UCONST only: 0 (u is [nC], shared), or B when u is [nC][B]: every trajectory under a constant control of its own
+  // (ocs_rk4inf_set_batch_ustar)
+  int ub;
 };
+// UCONST: control row g of the lane that holds trajectory b (b < B also for the lanes past a ragged batch end, which are clamped)
+__device__ static inline double lq_uconst(const LQArgs& a, int g, int b) {
+  return a.ub ? a.u[(size_t)g * a.ub + b] : a.u[g];
+}
 // k_lq_forward<RT, true, false, 0, false, SWEEP = true> on `a`, RT by a.nS (ocs_lq_kernels.hip)
 void lq_forward_one_wave(const LQArgs& a, hipStream_t s);
 

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64) void k_lq_forward(const LQArgs a) {
   const size_t ustride = (size_t)nC * B;
   const double* up = a.u + (UCONST ? 0 : (size_t)(2 * i0) * ustride) + (size_t)(uact ? g : 0) * B + b;  // u(:, 2 i0 + 1) of this lane's control row
   const unsigned vu = (unsigned)(((size_t)(uact ? g : 0) * B + b) * 8), us8 = (unsigned)(ustride * 8);
-  double uA = UCONST ? (uact ? a.u[g] : 0.0) : (uact ? *up : 0.0);
+  double uA = UCONST ? (uact ? lq_uconst(a, g, b) : 0.0) : (uact ? *up : 0.0);
   d4 buA[RT], buM[RT], buB[RT];
   P.bu_times(uA, buA);
   if (UCONST) {
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(64) void k_lq_backward(const LQArgs a) {
   const double* up = a.u + uoff;
   double* dq = a.dJdu + uoff;
   const unsigned vu = (unsigned)(uoff * 8), us8 = (unsigned)(ustride * 8), vdq = uact ? vu : kOffDrop;
-  double uB = UCONST ? (uact ? a.u[g] : 0.0) : (uact ? up[(size_t)(2 * N) * ustride] : 0.0);
+  double uB = UCONST ? (uact ? lq_uconst(a, g, b) : 0.0) : (uact ? up[(size_t)(2 * N) * ustride] : 0.0);
   double uA = uB, uM = uB;
   d4 buA[RT], buM[RT];
   P.bu_times(uB, buA);
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(256) void k_lq2_forward(const LQArgs a) {
   const unsigned us8 = (unsigned)(ustride * 8);
   const double* up = a.u + (size_t)(uact ? g : 0) * B + b;
   const unsigned vu = (unsigned)(((size_t)(uact ? g : 0) * B + b) * 8);
-  double uA = UCONST ? (uact ? a.u[g] : 0.0) : (uact ? *up : 0.0);
+  double uA = UCONST ? (uact ? lq_uconst(a, g, b) : 0.0) : (uact ? *up : 0.0);
   double uM = uA, uB = uA;
   if (!UCONST) {
     uM = uact ? up[ustride] : 0.0;
@@ -734,7 +734,7 @@ __global__ __launch_bounds__(256) void k_lq2_backward(const LQArgs a) {
   double* dq = a.dJdu + uoff;
   const unsigned vu = (unsigned)(uoff * 8), us8 = (unsigned)(ustride * 8);
   const unsigned vdq = (w == 0 && uact) ? vu : kOffDrop;
-  double uB = UCONST ? (uact ? a.u[g] : 0.0) : (uact ? up[(size_t)(2 * N) * ustride] : 0.0);
+  double uB = UCONST ? (uact ? lq_uconst(a, g, b) : 0.0) : (uact ? up[(size_t)(2 * N) * ustride] : 0.0);
   double uA = uB, uM = uB;
   if (!UCONST) {
     uA = uact ? up[(size_t)(2 * N - 2) * ustride] : 0.0;
@@ -1037,7 +1037,7 @@ __global__ __launch_bounds__(256) void k_lq4_forward(const LQArgs a) {
   const size_t ustride = (size_t)nC * B;
   const double* up = a.u + (size_t)(uact ? g : 0) * B + b;
   const unsigned vu = (unsigned)(((size_t)(uact ? g : 0) * B + b) * 8), us8 = (unsigned)(ustride * 8);
-  double uA = UCONST ? (uact ? a.u[g] : 0.0) : (uact ? *up : 0.0);
+  double uA = UCONST ? (uact ? lq_uconst(a, g, b) : 0.0) : (uact ? *up : 0.0);
   double uM = uA, uB = uA;
   d4 buA = bu_times(uA), buM = buA, buB = buA;
   double F1[4];
@@ -1217,7 +1217,7 @@ __global__ __launch_bounds__(256) void k_lq4_backward(const LQArgs a) {
   const double* up = a.u + uoff;
   double* dq = a.dJdu + uoff;
   const unsigned vu = (unsigned)(uoff * 8), us8 = (unsigned)(ustride * 8);
-  double uB = UCONST ? (uact ? a.u[g] : 0.0) : (uact ? up[(size_t)(2 * N) * ustride] : 0.0);
+  double uB = UCONST ? (uact ? lq_uconst(a, g, b) : 0.0) : (uact ? up[(size_t)(2 * N) * ustride] : 0.0);
   double uA = uB, uM = uB;
   if (!UCONST) {
     uA = uact ? up[(size_t)(2 * N - 2) * ustride] : 0.0;
@@ -1449,6 +1449,7 @@ struct LqWorkspace {
   double *zc = nullptr, *zz = nullptr;   // [C][nS][16]: the responses; zeros (their start states)
   size_t zc_cap = 0, zz_cap = 0;
   const double* zc_key_u = nullptr;
+  unsigned long long zc_key_uversion = 0;   // FwdOpts::uversion the responses were formed under
   bool zc_valid = false;
 };
 void lq_workspace_free(LqWorkspace* w) {
@@ -1643,14 +1644,19 @@ static int lq_forward_chunked(const ProblemDesc& p, const GridDesc& g, int batch
   LQArgs a{};
   a.N = N; a.batch = batch; a.nS = nS; a.nC = nC; a.REC = g.REC; a.ps = p.ps;
   a.x0 = x0; a.u = u; a.x = x; a.J = J; a.Jadd = o.Jadd; a.L = L; a.W = p.W;
+  a.ub = o.uconst && o.uconst_batch ? batch : 0;
   const dim3 grid((batch + 15) / 16, C), block(64);
   // pass Z: every chunk from a zero state (cs of the carries is not read: zeros through a memset); it forms no objective, so
   // it reads no weights and is the same kernel with and without per-trajectory weights, like the chunk matrices
   if (hipMemsetAsync(w->cs, 0, (size_t)C * nS * B * sizeof(double), s) != hipSuccess) return (int)hipErrorUnknown;
   a.cs = w->cs; a.ce = w->ce;
-  if (o.uconst) {
+  if (o.uconst && o.uconst_batch) {
+    // a constant control of its own per trajectory: so is the zero-start response -- pass Z over the real batch, as below
+    k_lq_forward<RT, false, true, 1><<<grid, block, 0, s>>>(a);
+    k_lq_carry<false><<<dim3((batch + 63) / 64), dim3(256), 0, s>>>(nS, nU, batch, C, w->MT, x0, w->ce, w->cs, nullptr, batch);
+  } else if (o.uconst) {
     // constant control: the zero-start response is one vector per chunk for the whole batch; kept with the matrices
-    if (!w->zc_valid || w->zc_key_u != u) {
+    if (!w->zc_valid || w->zc_key_u != u || w->zc_key_uversion != o.uversion) {
       if ((rc = lq_ensure(w->zc, w->zc_cap, (size_t)C * nS * 16))) return rc;
       if ((rc = lq_ensure(w->zz, w->zz_cap, (size_t)C * nS * 16))) return rc;
       if (hipMemsetAsync(w->zz, 0, (size_t)C * nS * 16 * sizeof(double), s) != hipSuccess) return (int)hipErrorUnknown;
@@ -1658,6 +1664,7 @@ static int lq_forward_chunked(const ProblemDesc& p, const GridDesc& g, int batch
       z.batch = 16; z.x = nullptr; z.J = nullptr; z.Jadd = nullptr; z.cs = w->zz; z.ce = w->zc;
       k_lq_forward<RT, false, true, 1><<<dim3(1, C), block, 0, s>>>(z);
       w->zc_key_u = u;
+      w->zc_key_uversion = o.uversion;
       w->zc_valid = true;
     }
     k_lq_carry<false><<<dim3((batch + 63) / 64), dim3(256), 0, s>>>(nS, nU, batch, C, w->MT, x0, w->zc, w->cs, nullptr, 16);
@@ -1691,6 +1698,7 @@ static int lq_backward_chunked(const ProblemDesc& p, const GridDesc& g, int batc
   LQArgs a{};
   a.N = N; a.batch = batch; a.nS = nS; a.nC = nC; a.REC = g.REC; a.ps = p.ps;
   a.xck = xck; a.u = u; a.lamT = lamT; a.L = L; a.W = p.W;
+  a.ub = o.uconst && o.uconst_batch ? batch : 0;
   const dim3 grid((batch + 15) / 16, C), block(64);
   // pass Z: the objective's share of every chunk map (zero costate at the chunk's last node) -- with the trajectory's own q
   a.ce = w->ce;
@@ -1724,6 +1732,8 @@ bool lq_supported(int nS, int nC) { return nS >= 1 && nS <= 32 && nC >= 1 && nC 
 // its own (the zero-start responses are one vector per chunk for the whole batch) and the adjoint wants nothing but lam2(:,1),
 // the value at the far end of the horizon -- pass Z and the carries ARE that pass, there is no pass X; no doubled work, so
 // chunks pay as soon as there are two of them (8192 trajectories: 4 chunks, 2048 one-wave groups instead of 1024 exchanging pairs).
+// With a uStar per trajectory (FwdOpts::uconst_batch) the responses differ per trajectory and the state pass runs a real pass Z
+// over the batch; the threshold is the shared form's (pass pair at 8192 trajectories 27.8 -> 34.8 ms, NOTES.md; not re-tuned).
 // Four waves per 16 trajectories (K-split): E = 4 always, E = 2 never; request 3 forces it.  Automatic: while the four waves
 // of a group still find SIMDs of their own (<= 4096 trajectories = 1024 waves).  Measured, nS = 32, nC = 4, 2 x 4000 steps, ms
 // state pass / adjoint pass, two waves -> four waves:
@@ -1789,6 +1799,7 @@ static int lq_forward_dispatch(const ProblemDesc& p, const GridDesc& g, int batc
   LQArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
   a.x0 = x0; a.u = u; a.x = x; a.J = J; a.Jadd = o.Jadd; a.W = p.W;
+  a.ub = o.uconst && o.uconst_batch ? batch : 0;
   switch (lq_mapping(g, p.nS, batch, o.mapping, o.uconst)) {
     case LqMap::Chunks:
       return p.nS <= 16 ? lq_forward_chunked<1, PW>(p, g, batch, x0, u, x, J, o, s) : lq_forward_chunked<2, PW>(p, g, batch, x0, u, x, J, o, s);
@@ -1835,6 +1846,7 @@ static int lq_backward_dispatch(const ProblemDesc& p, const GridDesc& g, int bat
   LQArgs a{};
   a.N = g.N; a.batch = batch; a.nS = p.nS; a.nC = p.nC; a.REC = g.REC; a.ps = p.ps;
   a.xck = xck; a.u = u; a.lamT = lamT; a.lam = lam; a.dJdu = dJdu; a.lam0 = o.lam0; a.W = p.W;
+  a.ub = o.uconst && o.uconst_batch ? batch : 0;
   switch (lq_mapping(g, p.nS, batch, o.mapping, o.uconst)) {
     case LqMap::Chunks:
       return p.nS <= 16 ? lq_backward_chunked<1, PW>(p, g, batch, xck, u, lamT, lam, dJdu, o, s)

@@ -56,7 +56,7 @@ struct FwdArgs {
   const double* pb;
   unsigned pmask;
   const double* x0;
-  const double* u;      // [2N+1][nC][B]; with UCONST: [nC], the same for every grid point and trajectory
+  const double* u;      // [2N+1][nC][B]; with UCONST: [nC], the same for every grid point and trajectory (or [nC][B]: `ub`)
   double* x;
   double* J;
   const double* Jadd;   // optional [B]: J = Jadd + x(end,end)  (RK4InfiniteIntegrator.m:23  J = J1 + J2)
@@ -66,6 +66,7 @@ struct FwdArgs {
                         //               kernel's last column; default 0, RK4Integrator.m:33)
   const int* gate = nullptr;   // optional: the launch does nothing if *gate == 0 (a sweep of fb_sweep enqueued before the
                                // host knew that the sweep before it had left no instance active)
+  int ub = 0;                  // UCONST only: 0, or B when u is [nC][B], a constant control of its own per trajectory
 };
 
 // Lanes past the end of the batch are clamped onto the last trajectory: they recompute it and
@@ -116,9 +117,9 @@ __global__ __launch_bounds__(64) void k_forward(const FwdArgs a) {
 
   const double* up = a.u;  // walks u(:,j) row by row
   double uprev[NC];
-  if (UCONST) {
+  if (UCONST) {  // loaded once, before the time loop: the shared vector through the scalar unit, or this lane's own column
 #pragma unroll
-    for (int c = 0; c < NC; ++c) uprev[c] = PSU(a.u)[c];
+    for (int c = 0; c < NC; ++c) uprev[c] = a.ub ? a.u[(size_t)c * B + b] : PSU(a.u)[c];
   } else {
     up += b;
 #pragma unroll
@@ -380,6 +381,7 @@ struct BwdArgs {
   double* lam;
   double* dJdu;
   double* lam0;         // optional [nAug][B]: lam(:,1) only (RK4InfiniteIntegrator.m:29, single_shooting.m:149)
+  int ub = 0;           // UCONST only: 0 (u is [nC]), or B when u is [nC][B] (see FwdArgs)
 };
 
 // XRC (checkpoint re-integration, as in the scan kernel, ocs_scan_kernel.hpp): of the CH checkpoints of a chunk only the first is
@@ -435,7 +437,7 @@ __global__ __launch_bounds__(64) void k_backward(const BwdArgs a) {
 #pragma unroll
   for (int c = NC - 1; c >= 0; --c) {
     if (UCONST) {
-      unext[c] = PSU(a.u)[c];
+      unext[c] = a.ub ? a.u[(size_t)c * B + b] : PSU(a.u)[c];
     } else {
       up -= B;
       unext[c] = *up;

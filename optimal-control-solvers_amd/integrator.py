@@ -213,18 +213,73 @@ def trajectory_status_dev(J, status=None):
     return status
 
 
+def split_uStar(uStar):
+    """What RK4InfiniteIntegrator's constructor makes of its uStar argument (no device needed): (shared, batch).
+    A scalar, a vector or a single column is the reference's uStar, nC values shared by every trajectory: (that vector,
+    None).  A matrix with more than one column is nC x B, a uStar per trajectory: (its column 0, the matrix)."""
+    a = np.asarray(uStar, dtype=np.float64)
+    if a.ndim > 2:
+        raise ValueError(f"uStar: expected nC values or an nC x B matrix, got shape {a.shape}")
+    if a.ndim == 2 and a.shape[1] > 1:
+        return _f(a[:, 0]).ravel(), _f(a)
+    if a.size < 1:
+        raise ValueError("uStar is empty")
+    return _f(np.atleast_1d(a)).ravel(), None
+
+
+def batch_uStar_host(U, nC):
+    """The host argument of set_batch_uStar as the library takes it: nC x B, column-major (no device needed).  A 1-D
+    array is refused: it does not say whether it is one trajectory's nC values or nC = 1 for B trajectories."""
+    a = np.asarray(U, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"uStar per trajectory: expected an nC x B matrix ({nC} x B), got {a.ndim}-D input of shape {a.shape}")
+    if a.shape[0] != nC or a.shape[1] < 1:
+        raise ValueError(f"uStar per trajectory: expected {nC} x B (nC of the integrator's uStar), got {a.shape[0]} x {a.shape[1]}")
+    return _f(a)
+
+
 class RK4InfiniteIntegrator(RK4Integrator):
     """Integrator/RK4InfiniteIntegrator.m:12-30: RK4 on tspan, then a tail leg on tspanExtra under
-    the constant control uStar; J = J1 + J2, terminal adjoint of leg 1 = lam2(:,1)."""
+    the constant control uStar; J = J1 + J2, terminal adjoint of leg 1 = lam2(:,1).
+
+    uStar: the reference's nC values, shared by every trajectory of a call -- or (batch extension, no counterpart in the
+    reference) an nC x B matrix with B > 1 columns, a constant tail control per trajectory: trajectory b is then integrated
+    as RK4InfiniteIntegrator(tspan, tspanExtra, uStar[:, b]) would, and calls must use batch B (see set_batch_uStar)."""
 
     def __init__(self, tspan, tspanExtra, uStar):
         self.tspan = _f(tspan).ravel()
         self.tspanExtra = _f(tspanExtra).ravel()
-        self.uStar = _f(np.atleast_1d(uStar)).ravel()
+        shared, batch = split_uStar(uStar)
+        self.uStar = shared if batch is None else batch
+        self.batch_uStar = None
         h = C.c_void_p()
         check(lib.ocs_rk4inf_create(C.byref(h), _p(self.tspan), self.tspan.size, _p(self.tspanExtra),
-                                    self.tspanExtra.size, _p(self.uStar), self.uStar.size))
+                                    self.tspanExtra.size, _p(shared), shared.size))
         self._finish_init(h)
+        self._nC = shared.size
+        if batch is not None:
+            self.set_batch_uStar(batch)
+
+    def set_batch_uStar(self, U=None):
+        """A constant tail control of its own per trajectory (e.g. the uStar of each instance's compute_equilibrium under
+        per-trajectory parameters): U is nC x B, a numpy array (host call) or a CUDA float64 tensor [nC][B] (device call,
+        asynchronous on the current stream; the values are copied into a buffer of the handle).  Compute calls on this
+        integrator must then use batch B.  No argument or None clears it: back to the shared uStar of the constructor."""
+        if U is None:
+            check(lib.ocs_rk4inf_set_batch_ustar(self._h, 0, None))
+            self.batch_uStar = None
+            return self
+        if torch.is_tensor(U):
+            if U.ndim != 2 or U.shape[0] != self._nC or U.shape[1] < 1 or not U.is_cuda or U.dtype != torch.float64 \
+                    or not U.is_contiguous():
+                raise ValueError(f"uStar per trajectory: expected a contiguous float64 CUDA tensor [{self._nC}][B], got "
+                                 f"{tuple(U.shape)} {U.dtype} on {U.device}")
+            check(lib.ocs_rk4inf_set_batch_ustar_dev(self._h, U.shape[1], _dptr(U), _stream()))
+        else:
+            U = batch_uStar_host(U, self._nC)
+            check(lib.ocs_rk4inf_set_batch_ustar(self._h, U.shape[1], _p(U)))
+        self.batch_uStar = U
+        return self
 
     def compute_adjoints(self, prob, u, nargout=2):
         return super().compute_adjoints(prob, u, None, nargout)

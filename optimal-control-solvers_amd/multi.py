@@ -3,7 +3,11 @@ hands whole batches to MultiDevice, which cuts them into contiguous blocks, runs
 device concurrently (no data-path exchange) and reduces [sum J, count] / (min J, argmin) over RCCL.
 
 The reference has no batch axis (tests/solve_test_problem.m:37 integrates one trajectory per call); arrays here are the
-MATLAB-shaped host arrays of the one-device calls with the batch as trailing dimension."""
+MATLAB-shaped host arrays of the one-device calls with the batch as trailing dimension.
+
+What belongs to a handle is per device: every device has its own problem, integrator and control handle.  A uStar per
+trajectory (RK4InfiniteIntegrator.set_batch_uStar) therefore has no ocs_multi_* entry point of its own -- set columns
+[lo, hi) of block k (shard(batch, k)) on device k's integrator, as for per-trajectory parameters on device k's problem."""
 from __future__ import annotations
 
 import ctypes as C

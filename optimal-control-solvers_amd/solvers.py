@@ -224,6 +224,31 @@ def compute_equilibrium_dev(prob, yGuess, lb, ub, r):
     return y, resnorm, res, flag
 
 
+def clamp_u0_batch(u0, bounds, B):
+    """The start control of single_shooting_batch, clamped to the control bounds (nC x 2): (u0c, per_instance).  u0 is nC
+    values (a scalar is repeated), shared by the B instances -> u0c has shape (nC,); or an nC x B matrix, one start per
+    instance (tests/solve_test_problem.m:37 passes uStar', here each instance's own) -> u0c is nC x B.  No device needed."""
+    bounds = np.asarray(bounds, dtype=np.float64)
+    nC = bounds.shape[0]
+    a = np.asarray(u0, dtype=np.float64)
+    per_instance = a.ndim == 2 and a.shape == (nC, B) and B > 1
+    if not per_instance:
+        if a.ndim > 2 or (a.ndim == 2 and min(a.shape) > 1):
+            raise ValueError(f"u0: expected nC = {nC} values or an nC x B = {nC} x {B} matrix, got shape {a.shape}")
+        a = np.broadcast_to(a.ravel(), (nC,))
+        return np.minimum(bounds[:, 1], np.maximum(bounds[:, 0], a)), False
+    return np.minimum(bounds[:, 1:2], np.maximum(bounds[:, 0:1], a)), True
+
+
+def initial_v_batch(control, u0, bounds, B):
+    """v0 of single_shooting_batch from u0 (clamp_u0_batch): compute_initial_v of the shared start repeated B times, or column
+    by column for a start per instance.  nV x B."""
+    u0c, per_instance = clamp_u0_batch(u0, bounds, B)
+    if not per_instance:
+        return np.repeat(control.compute_initial_v(u0c)[:, None], B, axis=1)
+    return np.stack([control.compute_initial_v(np.ascontiguousarray(u0c[:, b])) for b in range(B)], axis=1)
+
+
 def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrator=None, u0=0.0, TolX=1e-5,
                           TolFun=3e-4, MaxIter=500, memory=10, FreeInitStates=(), FreeStateBounds=None, v0=None,
                           constraints="warn"):
@@ -239,6 +264,8 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     is the same KKT point.  Stopping (per instance): ||P(v - g) - v||_inf <= TolFun or step <= TolX.
     Free initial states ride at the tail of v, starting at x0 (single_shooting.m:81-85), inside FreeStateBounds
     (nFree x 2, :91-94; default unbounded).
+    u0: nC values shared by the instances, or nC x B, a start per instance (each instance's own uStar, as
+    tests/solve_test_problem.m:37 passes 'u0', uStar'); clamped to the bounds and expanded with compute_initial_v.
     Returns a dict of device tensors: v [nV(+nFree)][B], J [B], iterations [B], converged [B],
     projected_gradient [B], x0 [nS][B] and `soln_of(b)` (J, v and the control callable of instance b)."""
     from ._lib import SsOptions
@@ -252,9 +279,7 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     x0d = torch.tensor(x0, device=dev).contiguous()
     nFree, fis = _fis(FreeInitStates)
     if v0 is None:
-        u0c = np.minimum(prob.ControlBounds[:, 1], np.maximum(prob.ControlBounds[:, 0],
-                                                               np.broadcast_to(np.asarray(u0, dtype=np.float64).ravel(), (nC,))))
-        v0 = np.repeat(control.compute_initial_v(u0c)[:, None], B, axis=1)
+        v0 = initial_v_batch(control, u0, prob.ControlBounds, B)
     else:
         v0 = np.asarray(v0, dtype=np.float64)
         v0 = np.repeat(v0[:, None], B, axis=1) if v0.ndim == 1 else v0
