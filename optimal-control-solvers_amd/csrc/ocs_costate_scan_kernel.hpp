@@ -71,9 +71,13 @@ __global__ __launch_bounds__(W * 64) void k_costate_scan(const CostateScanArgs a
   const int N = a.N;
   if (a.gate && *a.gate == 0) return;
   const int b = tile_base(blockIdx.x, TPW, a.batch) + tl;   // (a ragged last tile overlaps its neighbour)
+  // MET reads the costate of the sweep before from the buffer it overwrites: ordered inside a workgroup only, so every
+  // instance has ONE owner.  The lanes of a ragged last tile below the workgroup's own tile are the neighbour's: they are
+  // computed along (the rows of an instance meet in the lane sums) but store nothing and take no part in the bookkeeping.
+  const bool own = !MET || b >= (int)blockIdx.x * TPW;
   const uniform_ptr PS = as_uniform(a.ps);
   const typename P::RowPar rp = P::load_row(ParamSrc{PS, a.pb, a.pmask, B, b}, r);
-  const bool fz = a.frozen != nullptr && a.frozen[b] != 0;
+  const bool fz = !own || (a.frozen != nullptr && a.frozen[b] != 0);   // no stores of lam
   const size_t colB = (size_t)G * B, xcolB = (size_t)a.ldx * B;
   const unsigned col8 = (unsigned)(colB * 8);
   const unsigned vrow = (unsigned)(((size_t)r * B + b) * 8);
@@ -295,7 +299,7 @@ __global__ __launch_bounds__(W * 64) void k_costate_scan(const CostateScanArgs a
     any = any || oa;
   }
   bool still = false;
-  if (r == 0 && a.status[b] == 0) {
+  if (r == 0 && own && a.status[b] == 0) {
     const double mx = any ? nmax / dmax : __builtin_nan("");
     a.maxChange[(size_t)(a.sweep - 1) * B + b] = mx;
     if (mx <= 1.0)

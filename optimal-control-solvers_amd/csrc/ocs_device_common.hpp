@@ -11,9 +11,13 @@ namespace ocs {
 #define OCS_INLINE __attribute__((always_inline))
 
 // First trajectory of a workgroup's tile of TPW trajectories.  A batch that is not a multiple of the tile: the LAST workgroup takes
-// the last TPW trajectories, overlapping its neighbour -- the overlap is computed twice with the same operations and stored twice
-// with the same values (the tiled kernels accumulate nothing across trajectories; counters of active instances may count an
-// instance twice, they are only compared with zero).  Launchers ask for it with batch > TPW and an even batch (16-byte DMA chunks).
+// the last TPW trajectories, overlapping its neighbour -- the overlap is computed twice with the same operations (the tiled
+// kernels accumulate nothing across trajectories).  A kernel that writes only arrays it does not read (the state passes: x, J from
+// x0, u or lam; the plain costate passes: lam from x) stores the overlap twice with the same values.  A kernel that reads an array
+// it also writes must NOT: nothing orders the two workgroups, and the later one would read what the earlier one stored.  The costate
+// passes that carry the sweep's convergence test (k_costate_scan<MET>, k_costate_plx<MET>: lam replaced in place, status, maxChange,
+// the counter of active instances) give an overlapped trajectory ONE owner -- the lanes with b < block * TPW of the last workgroup are
+// the neighbour's and store nothing.  Launchers ask for the overlap with batch > TPW and an even batch (16-byte DMA chunks).
 __device__ static inline int tile_base(int block, int TPW, int batch) {
   const int b0 = block * TPW;
   return b0 + TPW <= batch ? b0 : batch - TPW;

@@ -659,6 +659,10 @@ __global__ __launch_bounds__(MET ? 576 : 320) void k_costate_plx(const CostateXA
   }
   const int r = lane % G, tl = lane / G;
   const int b = bw + tl;
+  // MET reads the costate of the sweep before from the buffer it overwrites (ordered inside a workgroup only): every instance
+  // has ONE owner.  The lanes of a ragged last tile below the workgroup's own tile are the neighbour's: computed along, but
+  // they store no costate and take no part in the bookkeeping (k_costate_scan has the same rule).
+  const bool own = !MET || b >= (int)blockIdx.x * TPW;
   if (MET && wave == 7) {   // keeps the recursion wave alone on its SIMD (waves w, w + 4, ..): takes part in the barriers only
     for (int k = 0; k <= nb + 3; ++k) lds_barrier();
     return;
@@ -739,7 +743,7 @@ __global__ __launch_bounds__(MET ? 576 : 320) void k_costate_plx(const CostateXA
     }
     // fb_sweep.m:108-110 and :79-87 (k_fbs_advance): every other wave of this workgroup read the status when it started
     bool still = false;
-    if (r == 0 && aa.status[b] == 0) {
+    if (r == 0 && own && aa.status[b] == 0) {
       const double mx = any ? nmax / dmax : __builtin_nan("");
       aa.maxChange[(size_t)(aa.sweep - 1) * B + b] = mx;
       if (mx <= 1.0)
@@ -761,7 +765,7 @@ __global__ __launch_bounds__(MET ? 576 : 320) void k_costate_plx(const CostateXA
       costate_midpoints<C_, 3, false>(inp, xm, 3, N, r, tl, lane, xN, lr, nullptr, 0, true);
     else  // the helper with the shortest run also stores lam
       costate_midpoints<C_, 2, true>(inp, xm, 6, N, r, tl, lane, xN, lr, a.lam + (size_t)r * B + b, (size_t)G * B,
-                                     FRZ && a.frozen[b] != 0);
+                                     !own || (FRZ && a.frozen[b] != 0));
     if (MET) lds_barrier();
     return;
   }
@@ -770,7 +774,7 @@ __global__ __launch_bounds__(MET ? 576 : 320) void k_costate_plx(const CostateXA
   const typename P::RowPar rp = P::load_row([&](int k) OCS_INLINE {
     return ((a.pmask >> k) & 1u) ? a.pb[(size_t)k * B + b] : PS[k];
   }, r);
-  const bool fz = FRZ && a.frozen[b] != 0;
+  const bool fz = !own || (FRZ && a.frozen[b] != 0);   // (only the store of lam(t_N) looks at it here)
   const size_t colB = (size_t)G * B;
   double l = 0.0;
   double xB = xN;

@@ -64,11 +64,13 @@ def draw_case(rng, case, ocs, ragged=False):
 
 
 def run_case(ocs, oracle, c, nsweeps=60, oracle_instances=None):
-    """-> dict(ok, sweeps, err_fold, err_oracle, worst: description of the worst converged instance, failures: list)"""
+    """-> dict(ok, sweeps, err_fold, err_oracle, worst: description of the worst converged instance, failures: list,
+    path: ocs.fb_sweep_path of the default run, 4 = the folded sweep)"""
     prob = ocs.LogisticProblem(c["m"], P["c"], P["r"], c["bounds"])
     prob.set_batch_params([0], c["cs"][None, :])
     base = {"nERROR_PTS": c["N"] + 1, "nINTERP_PTS": 17, "nSWEEPS": nsweeps, "cost_row": c["cost_row"]}
-    ra = ocs.fb_sweep_batch(prob, c["x0"], c["tspan"], dict(base))
+    ga = ocs.RK4Integrator(c["tspan"])
+    ra = ocs.fb_sweep_batch(prob, c["x0"], c["tspan"], dict(base), integrator=ga)
     rd = ocs.fb_sweep_batch(prob, c["x0"], c["tspan"], dict(base, fused_update_off=3))
     sw = ra["sweeps"]
     fails = []
@@ -104,7 +106,7 @@ def run_case(ocs, oracle, c, nsweeps=60, oracle_instances=None):
         if not e < 1e-10:
             fails.append(f"instance {b} ({sw[b]} sweeps): vs oracle {e:.2e}")
     return dict(ok=not fails, sweeps=sw, err_fold=err_fold, err_oracle=err_or, worst=worst, failures=fails,
-                checked=len(oracle_instances))
+                checked=len(oracle_instances), path=ocs.fb_sweep_path(ga))
 
 
 if __name__ == "__main__":

@@ -16,6 +16,21 @@ def relerr(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))))
 
 
+def max_change_err(mca, mcb, sweeps):
+    """maxChange [nSWEEPS][batch] of two runs with the same sweep counts: the largest relerr over maxChange[:sweeps[b], b]
+    of every instance (all nSWEEPS rows of an instance that did not converge).  NaN where a value is missing."""
+    k = np.where(sweeps > 0, sweeps, mca.shape[0])
+    own = np.arange(mca.shape[0])[:, None] < k[None, :]
+    return relerr(np.where(own, mca, 0.0), np.where(own, mcb, 0.0))
+
+
+def nan_pattern_ok(mc, sweeps):
+    """maxChange [nSWEEPS][batch]: finite up to an instance's own convergence sweep, NaN after it."""
+    k = np.where(sweeps > 0, sweeps, mc.shape[0])
+    own = np.arange(mc.shape[0])[:, None] < k[None, :]
+    return bool(np.all(np.isfinite(mc[own])) and np.all(np.isnan(mc[~own])))
+
+
 @pytest.fixture(scope="module")
 def ocs():
     import torch
@@ -374,17 +389,28 @@ def test_numpy_linspace_grid_takes_the_same_path(ocs, oracle):
         assert abs(rb["J"][b] - ref["J"]) < RTOL * abs(ref["J"]) and relerr(rb["lam"][:, :, b], ref["lam"]) < RTOL
 
 
+STRESS_RAGGED = (1, 10, 19)   # two, one and four states: 60, 108 and 54 instances on 32, 24 and 24 steps
+
+
 def test_fold_stress_per_instance(ocs, oracle):
     """fb_sweep.m:79-87, 99-115 on randomly drawn problems, checked PER INSTANCE (tests/stress_fold.py): the folded
     kernels, the unfolded path and the oracle agree on the sweep count of every instance (0 = not converged, the
     reference's empty struct); every converged instance -- the cases drawn here hold instances that need 26 to 59 sweeps
     (lower bound -0.2) next to instances that never converge -- meets 1e-11 fold-vs-unfolded and 1e-10 against
-    oracle.fb_sweep (the three slowest-converging instances of a case, both ends of the batch, one that fails)."""
+    oracle.fb_sweep (the three slowest-converging instances of a case, both ends of the batch, one that fails).
+    Cases RAGGED of the same sequence get draw_case's ragged tail (an even number of further instances from a generator of
+    their own: the last workgroup overlaps its neighbour, and every other case keeps its draws): the same checks per
+    instance, sweep counts and maxChange included, on the folded path."""
     from tests import stress_fold
     rng = np.random.default_rng(1)
     want = {3: 26, 13: 40, 21: 26, 25: 40, 33: 38}     # case -> sweeps at least one converged instance needs
     for case in range(max(want) + 1):
-        c = stress_fold.draw_case(rng, case, ocs)
+        c = stress_fold.draw_case(rng, case, ocs, ragged=case in STRESS_RAGGED)
+        if case in STRESS_RAGGED:
+            assert c["batch"] % (64 // c["nS"]) != 0 and c["batch"] % 2 == 0 and c["kind"] < 2
+            r = stress_fold.run_case(ocs, oracle, c)
+            assert r["ok"] and r["path"] == 4, (case, r["path"], r["failures"][:4])
+            assert r["err_fold"] < 1e-11 and r["err_oracle"] < 1e-10
         if case not in want:
             continue
         r = stress_fold.run_case(ocs, oracle, c)
@@ -414,6 +440,9 @@ def test_two_kernel_sweep_on_ragged_batches(ocs, oracle, nS, batch):
     assert np.array_equal(ra["sweeps"], rb["sweeps"]) and ra["sweeps"].min() > 0
     for key in ("x", "lam", "u", "J"):
         assert relerr(ra[key], rb[key]) < 1e-12, key
+    # the recorded change of the control, every instance up to its own sweep (the overlapped ones have ONE owner workgroup)
+    assert max_change_err(ra["maxChange"], rb["maxChange"], ra["sweeps"]) < 1e-6
+    assert nan_pattern_ok(ra["maxChange"], ra["sweeps"])
     for b in (0, batch - 2, batch - 1):
         ref = oracle.fb_sweep(oracle.LogisticProblem(m, cs[b], P["r"], BOUNDS), x0[:, b], tspan, base)
         assert ra["sweeps"][b] == ref["_sweeps"] and abs(ra["J"][b] - ref["J"]) < RTOL * abs(ref["J"])
@@ -501,3 +530,147 @@ def test_two_kernel_sweep_beyond_512_workgroups(ocs, oracle, nS, batch):
         ref = oracle.fb_sweep(oracle.LogisticProblem(m, cs[b], P["r"], BOUNDS), x0[:, b], tspan, base)
         assert ra["sweeps"][b] == ref["_sweeps"] and abs(ra["J"][b] - ref["J"]) < RTOL * abs(ref["J"])
         assert relerr(ra["x"][:, :, b], ref["x"]) < RTOL and relerr(ra["u"][:, :, b], ref["u"]) < RTOL
+
+
+# ---- ragged batches of the folded sweep: one owner workgroup per instance --------------------------------------------------------
+# The last workgroup of a ragged launch takes the LAST tile and overlaps its neighbour (tile_base, ocs_device_common.hpp).  The
+# costate pass that carries the convergence test (k_costate_scan<MET> up to 128 tiles, k_costate_plx<MET> beyond) reads the
+# costate of the sweep before from the buffer it overwrites, so an overlapped instance must have ONE workgroup that stores
+# its costate and does its bookkeeping: a second one that starts late would read the new costate as the old one, find no
+# change of the control and freeze the instance a sweep early with a maxChange that is too small.
+#
+# Sizing of the batches that need several rounds of workgroups.  Both kernels of a folded sweep hold one workgroup per CU:
+#   k_costate_plx<MET>   static LDS 7 slots x 1408 doubles (step records 128, interval records 128, x rows 512, rows of
+#                        the old costate 512, time coefficients 128) = 78 848 B, + xm 8192 + lr 8192 + xres 4608
+#                        = 99 840 B of the CU's 160 KiB (163 840 B): one workgroup (two need 199 680 B); its 9 waves
+#                        leave the 32 wave slots of a CU (8 per SIMD) far from being the limit;
+#   k_forward_cc         static LDS 146 432 B (nS = 1), 140 032 B (nS = 2), 129 152 B (nS = 4), each more than half of
+#                        the 160 KiB: one workgroup; 16, 12 and 8 waves.
+# (k_costate_scan<MET>, 16 waves, takes the launches of up to 128 tiles, which fit the device in any case.)
+# So the 256 CUs of the device hold 256 workgroups at once, and a launch of 1025 workgroups -- 1024 whole tiles and the
+# ragged one, dispatched last -- exceeds that four times over (the condition asked for: at least twice).  In instances:
+# 1024 tiles of 64 / nS plus a remainder of 2.
+RESIDENT_WG = 256 * 1
+RAGGED_MULTI_ROUND = {1: 1024 * 64 + 2, 2: 1024 * 32 + 2, 4: 1024 * 16 + 2}     # 65538, 32770, 16386 instances
+RAGGED_SHAPES = ([(nS, 8, 64 // nS + 2) for nS in (1, 2, 4)] +                   # one tile and two: the largest overlap
+                 [(nS, 8, 1000) for nS in (1, 2, 4)] +
+                 [(nS, 8, RAGGED_MULTI_ROUND[nS]) for nS in (1, 2, 4)] +
+                 [(nS, 16, 64 // nS + 2) for nS in (1, 2, 4)] +
+                 [(nS, 16, RAGGED_MULTI_ROUND[nS]) for nS in (1, 2, 4)])
+RAGGED_OPTS = lambda N: {"nERROR_PTS": N + 1, "nINTERP_PTS": 17, "nSWEEPS": 40}
+_ragged_runs = {}
+
+
+def ragged_fold_run(ocs, oracle, nS, N, batch):
+    """The folded sweep on a ragged batch of the registry logistic problem, every instance with its own c and x0; run
+    once per shape and shared (not modified) by the tests below."""
+    key = (nS, N, batch)
+    if key not in _ragged_runs:
+        rng = np.random.default_rng([nS, N, batch])
+        m = [3.0, 2.5, 2.0, 1.5][:nS]
+        tspan = oracle.linspace(0, 1.0, N + 1)
+        x0 = rng.uniform(0.8, 2.0, (nS, batch))
+        cs = rng.uniform(1.0, 2.0, batch)
+        prob = ocs.LogisticProblem(m, P["c"], P["r"], BOUNDS)
+        prob.set_batch_params([0], cs[None, :])
+        g = ocs.RK4Integrator(tspan)
+        r = ocs.fb_sweep_batch(prob, x0, tspan, RAGGED_OPTS(N), integrator=g)
+        tile = 64 // nS
+        assert ocs.fb_sweep_path(g) == 4 and batch % tile != 0 and batch % 2 == 0 and batch > tile
+        if batch == RAGGED_MULTI_ROUND[nS]:
+            assert -(-batch // tile) > 2 * RESIDENT_WG
+        _ragged_runs[key] = dict(m=m, tspan=tspan, x0=x0, cs=cs, r=r)
+    return _ragged_runs[key]
+
+
+def assert_bit_equal_on(ra, rp, batch):
+    """the first `batch` instances of rp against ra: sweeps, x, lam, u, J and the whole maxChange array, bit for bit"""
+    assert np.array_equal(ra["sweeps"], rp["sweeps"][:batch])
+    for key in ("x", "lam", "u", "J"):
+        assert np.array_equal(ra[key], rp[key][..., :batch], equal_nan=True), key
+    assert np.array_equal(ra["maxChange"], rp["maxChange"][:, :batch], equal_nan=True)
+
+
+def padded(a, n):
+    """a [.., batch] with n repeats of its last instance behind it"""
+    return np.concatenate([a, np.repeat(a[..., -1:], n, axis=-1)], axis=-1)
+
+
+@pytest.mark.parametrize("nS,N,batch", RAGGED_SHAPES)
+def test_ragged_fold_equals_the_whole_tile_fold_bit_for_bit(ocs, oracle, nS, N, batch):
+    """A ragged batch against the same instances in a batch padded (with repeats of the last instance) to whole tiles, both
+    on the folded sweep (path 4).  The kernels accumulate nothing across instances and the operations per instance are
+    the same whatever the batch, so the first `batch` instances agree bit for bit: x, lam, u, J, the sweep counts and the
+    whole maxChange array (NaN in the same places).  Shapes: one tile and two instances (the largest overlap), 1000, and a
+    batch of 1025 workgroups -- four times what the device holds at once (arithmetic above), the ragged workgroup
+    dispatched last --; N = 8, the smallest grid the fold takes (a kernel is short: a late workgroup starts after its
+    neighbour has stored), and 16."""
+    c = ragged_fold_run(ocs, oracle, nS, N, batch)
+    tile = 64 // nS
+    pad = -batch % tile
+    prob = ocs.LogisticProblem(c["m"], P["c"], P["r"], BOUNDS)
+    prob.set_batch_params([0], padded(c["cs"], pad)[None, :])
+    gp = ocs.RK4Integrator(c["tspan"])
+    rp = ocs.fb_sweep_batch(prob, padded(c["x0"], pad), c["tspan"], RAGGED_OPTS(N), integrator=gp)
+    assert ocs.fb_sweep_path(gp) == 4 and (batch + pad) % tile == 0 and 0 < pad < tile
+    assert c["r"]["sweeps"].min() > 0
+    assert_bit_equal_on(c["r"], rp, batch)
+
+
+@pytest.mark.parametrize("nS,N,batch", RAGGED_SHAPES)
+def test_ragged_fold_equals_the_kernel_sequence_and_the_oracle(ocs, oracle, nS, N, batch):
+    """The same ragged runs against the kernel-by-kernel sequence (fused_update_off = 1, path 1: no workgroup overlaps
+    another there): equal sweep counts -- the draws need 6 to 8 sweeps, differently many inside a batch, so an instance
+    frozen early shows as a wrong count --, x, lam, u, J to 1e-12, maxChange of every instance up to its own sweep to
+    1e-6 (its values divide by relTol |u| + absTol ~ 1e-7..1e-3: tests/stress_fold.py), finite up to that sweep and NaN
+    after it.  The oracle on the first instance, the first overlapped one and the last two."""
+    c = ragged_fold_run(ocs, oracle, nS, N, batch)
+    ra, tile = c["r"], 64 // nS
+    prob = ocs.LogisticProblem(c["m"], P["c"], P["r"], BOUNDS)
+    prob.set_batch_params([0], c["cs"][None, :])
+    gb = ocs.RK4Integrator(c["tspan"])
+    rb = ocs.fb_sweep_batch(prob, c["x0"], c["tspan"], dict(RAGGED_OPTS(N), fused_update_off=1), integrator=gb)
+    assert ocs.fb_sweep_path(gb) == 1
+    assert np.array_equal(ra["sweeps"], rb["sweeps"]) and ra["sweeps"].min() >= 2
+    assert batch < 1000 or len(set(ra["sweeps"].tolist())) > 1
+    for key in ("x", "lam", "u", "J"):
+        assert relerr(ra[key], rb[key]) < 1e-12, key
+    assert max_change_err(ra["maxChange"], rb["maxChange"], ra["sweeps"]) < 1e-6
+    assert nan_pattern_ok(ra["maxChange"], ra["sweeps"])
+    for b in (0, batch - tile, batch - 2, batch - 1):
+        ref = oracle.fb_sweep(oracle.LogisticProblem(c["m"], c["cs"][b], P["r"], BOUNDS), c["x0"][:, b], c["tspan"],
+                              RAGGED_OPTS(N))
+        assert ra["sweeps"][b] == ref["_sweeps"] and abs(ra["J"][b] - ref["J"]) < RTOL * abs(ref["J"])
+        assert relerr(ra["x"][:, :, b], ref["x"]) < RTOL and relerr(ra["u"][:, :, b], ref["u"]) < RTOL
+
+
+@pytest.mark.parametrize("nS,N,batch", [(2, 8, 34), (2, 8, 1000)])
+def test_ragged_fold_of_the_plugin_form(ocs, oracle, nS, N, batch):
+    """The hipRTC instance of the same costate kernel (k_costate_scan<UserP, .., MET>: a problem given as row functions
+    whose ControlChar reads the costate alone, flag bit 2) on ragged shapes of the tests above.  Row functions read the
+    shared parameter block only, so here the instances differ in x0 alone (c = 1.5 for all).  Bit for bit the plugin's
+    own whole-tile run; against the registry problem on the same ragged batch equal sweep counts, x, lam, u, J to the
+    1e-10 the plugin tests hold the two forms to (the row functions sum in another order than the registry kernels),
+    maxChange to 1e-6."""
+    from tests.user_problems import LOGISTIC_ROWS_CC_SRC
+    c = ragged_fold_run(ocs, oracle, nS, N, batch)      # (its x0 and grid)
+    tile = 64 // nS
+    pad = -batch % tile
+    runs = []
+    for n in (0, pad):
+        pu = ocs.UserProblem(LOGISTIC_ROWS_CC_SRC, nS, 1, [P["c"], P["r"]] + c["m"], BOUNDS, has_control_char=True,
+                             row_separable=True, control_from_costate=True)
+        g = ocs.RK4Integrator(c["tspan"])
+        runs.append(ocs.fb_sweep_batch(pu, padded(c["x0"], n), c["tspan"], RAGGED_OPTS(N), integrator=g))
+        assert ocs.fb_sweep_path(g) == 4
+    ru, rp = runs
+    assert_bit_equal_on(ru, rp, batch)
+    gr = ocs.RK4Integrator(c["tspan"])
+    rr = ocs.fb_sweep_batch(ocs.LogisticProblem(c["m"], P["c"], P["r"], BOUNDS), c["x0"], c["tspan"], RAGGED_OPTS(N),
+                            integrator=gr)
+    assert ocs.fb_sweep_path(gr) == 4
+    assert np.array_equal(ru["sweeps"], rr["sweeps"]) and ru["sweeps"].min() >= 2
+    for key in ("x", "lam", "u", "J"):
+        assert relerr(ru[key], rr[key]) < 1e-10, key
+    assert max_change_err(ru["maxChange"], rr["maxChange"], ru["sweeps"]) < 1e-6
+    assert nan_pattern_ok(ru["maxChange"], ru["sweeps"])
