@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void k_spg_direction(SpgArgs a) {
     const double v = a.v[i * B + b], g = a.g[i * B + b];
     const double d = spg_proj(v - alpha * g, a.lb[i], a.ub[i]) - v;
     a.d[i * B + b] = d;
-    a.vt[i * B + b] = v + d;
+    a.vt[i * B + b] = spg_proj(v + d, a.lb[i], a.ub[i]);  // v + (lb - v) can round to one ulp outside the box
     gtd += g * d;
   }
   double fmx = a.hist[b];
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void k_spg_accept(SpgArgs a) {
   }
   const double half = 0.5 * lam;
   a.lam[b] = half;
-  for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = a.v[i * B + b] + half * a.d[i * B + b];
+  for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = spg_proj(a.v[i * B + b] + half * a.d[i * B + b], a.lb[i], a.ub[i]);
   atomicAdd(a.counter, 1);
 }
 

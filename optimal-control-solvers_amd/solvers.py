@@ -251,7 +251,7 @@ def initial_v_batch(control, u0, bounds, B):
 
 def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrator=None, u0=0.0, TolX=1e-5,
                           TolFun=3e-4, MaxIter=500, memory=10, FreeInitStates=(), FreeStateBounds=None, v0=None,
-                          constraints="warn"):
+                          constraints="warn", maxBacktracks=None):
     """Batched direct single shooting: B independent NLPs  min_v J_b(v), Lb <= v <= Ub  --
     one per column of x0 and/or per per-trajectory parameter set of `prob` -- solved together on the GPU by the
     library's ocs_single_shooting_batch_dev.
@@ -262,6 +262,8 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     every instance with its own step length and stopping test, every objective/gradient evaluation one call
     of the hot path (nlpObjective) over the whole batch.  Iterates differ from fmincon's; the optimum
     is the same KKT point.  Stopping (per instance): ||P(v - g) - v||_inf <= TolFun or step <= TolX.
+    maxBacktracks: objective evaluations of one line search (default: that of ocs_ss_default_options); an instance
+    whose line search runs out of them stops where it is.
     Free initial states ride at the tail of v, starting at x0 (single_shooting.m:81-85), inside FreeStateBounds
     (nFree x 2, :91-94; default unbounded).
     u0: nC values shared by the instances, or nC x B, a start per instance (each instance's own uStar, as
@@ -314,6 +316,8 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     o = SsOptions()
     check(lib.ocs_ss_default_options(C.byref(o)))
     o.TolX, o.TolFun, o.MaxIter, o.memory = float(TolX), float(TolFun), int(MaxIter), int(memory)
+    if maxBacktracks is not None:
+        o.maxBacktracks = int(maxBacktracks)
     rc = lib.ocs_single_shooting_batch_dev(integrator._h, prob._h, control._h, B, _dptr(x0d), _dptr(v), nFree, fis,
                                            _p(Lb), _p(Ub), C.byref(o), _dptr(J), C.c_void_p(iters.data_ptr()), C.c_void_p(conv.data_ptr()), _dptr(pgn),
                                            _stream())
