@@ -284,13 +284,24 @@ int ocs_nlp_objective_dev(ocs_integrator g, ocs_problem p, ocs_control c, int ba
  * projected gradient: Barzilai-Borwein step, projection on [Lb, Ub] (compute_nlp_bounds), non-monotone Armijo
  * back-tracking; every instance has its own step length, line search and stopping test
  * ||P(v - g) - v||_inf <= TolFun or ||step||_inf <= TolX; every evaluation is one nlpObjective over the batch.
- * Iterates differ from fmincon's, the KKT point does not. */
+ * Iterates differ from fmincon's, the KKT point does not.
+ * algorithm = OCS_SS_LBFGS (the reference's 'Algorithm' option, single_shooting.m:22) selects a projected
+ * limited-memory BFGS per instance instead: coefficients on a bound with the gradient pushing outward are held, the
+ * two-loop recursion over the last `pairs` (s, y) pairs runs on the others, the line search is a monotone Armijo search
+ * along the projected path P(v + lam d); while no pair is held, and after a direction that is not a descent direction or
+ * a failed line search dropped them, the direction is SPG's.  Evaluations, stopping tests and outputs are the same. */
+#define OCS_SS_SPG 0
+#define OCS_SS_LBFGS 1
+/* Fill the struct with ocs_ss_default_options before setting fields: it has grown at its end between builds (algorithm
+ * and pairs are the latest members) and may again; a caller compiled against an older header passes a shorter struct. */
 typedef struct {
   double TolX;        /* single_shooting.m:20 */
   double TolFun;      /* :21 */
   int MaxIter;        /* outer iterations per instance */
-  int memory;         /* objective values the non-monotone line search looks back on */
+  int memory;         /* objective values the non-monotone line search looks back on (SPG only) */
   int maxBacktracks;  /* step halvings before an instance gives up */
+  int algorithm;      /* OCS_SS_SPG (default) or OCS_SS_LBFGS */
+  int pairs;          /* OCS_SS_LBFGS: (s, y) pairs kept per instance, 1..16 (default 8) */
 } ocs_ss_options;
 int ocs_ss_default_options(ocs_ss_options *o);
 /* device arrays, batch-minor: x0 nS x batch (overwritten at FreeInitStates), v (nV+nFree) x batch: start -> solution;

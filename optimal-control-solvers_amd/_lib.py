@@ -149,7 +149,10 @@ class FbsOptions(C.Structure):
 class SsOptions(C.Structure):
     """struct ocs_ss_options (include/ocs.h)."""
     _fields_ = [("TolX", C.c_double), ("TolFun", C.c_double), ("MaxIter", C.c_int), ("memory", C.c_int),
-                ("maxBacktracks", C.c_int)]
+                ("maxBacktracks", C.c_int), ("algorithm", C.c_int), ("pairs", C.c_int)]
+
+
+SS_ALGORITHMS = {"spg": 0, "lbfgs": 1}      # OCS_SS_SPG, OCS_SS_LBFGS
 
 
 def declared_symbols():

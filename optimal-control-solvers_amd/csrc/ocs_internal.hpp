@@ -297,6 +297,19 @@ struct SpgArgs {
 };
 // which: 0 init, 1 stopping test + direction + first trial, 2 Armijo test + next trial, 3 take the step, 4 verdict
 int launch_spg(int which, const SpgArgs& a, int it, double* pgnorm, int* converged, hipStream_t s);
+// projected L-BFGS on the same state (alpha, the trial point and the flags are SPG's; hist and fmax are unused; gtd holds
+// g'(vt - v) of the current trial point): per-instance ring of (s, y) pairs
+struct LbfgsArgs {
+  SpgArgs a;
+  int pairs;
+  double *S, *Y;      // [pairs][nV][B]
+  double *rho, *al;   // [pairs][B]: 1 / s'y of the stored pair; first-loop coefficients, newest pair first
+  int *fr;            // [nV][B] free coefficients of the current iterate
+  int *head, *count, *qn;  // [B] next slot, pairs held, the direction of this iteration is a quasi-Newton one
+};
+// which: 1 stopping test + active set + direction + first trial, 2 Armijo test + next trial, 3 take the step + pair store
+// (init and verdict are launch_spg's 0 and 4)
+int launch_lbfgs(int which, const LbfgsArgs& l, hipStream_t s);
 int control_grid_parts(int N);
 // batched vectorInterpolant: V [n][nComp][B] -> out [nq][nComp][B]; method as OCS_INTERP_*; t: tables of the sample grid
 int launch_interp(int method, const FbsTables& t, int nComp, int nq, const int* KQ, const double* SQ, int batch,

@@ -5,6 +5,10 @@
 // bounds of compute_nlp_bounds, non-monotone Armijo back-tracking) in which every instance keeps its own step
 // length, line search and stopping test, and every objective / gradient evaluation is one call of the hot path
 // (nlpObjective, :137-150) over the whole batch.  Iterates differ from fmincon's; the KKT point is the same.
+// ocs_ss_options.algorithm = OCS_SS_LBFGS selects a second outer iteration with the same evaluations, stopping tests and
+// outputs: a projected limited-memory BFGS per instance (two-loop recursion on the coefficients that are not held on a
+// bound, monotone Armijo search along the projected path, SPG's direction while no pair is held); tests/lbfgs_twin.py
+// states it step by step.
 #include "ocs_trace.hpp"
 #include "ocs_handles.hpp"
 
@@ -22,6 +26,8 @@ int ocs_ss_default_options(ocs_ss_options* o) {
   o->MaxIter = 500;
   o->memory = 10;
   o->maxBacktracks = 25;
+  o->algorithm = OCS_SS_SPG;
+  o->pairs = 8;
   return OCS_OK;
 }
 
@@ -37,6 +43,10 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
   if (!g || !p || !c || !x0 || !v || !opt || !J || batch < 1 || nFree < 0) return fail(OCS_ERR_INVALID, "bad argument");
   if (opt->MaxIter < 0 || opt->memory < 1 || opt->maxBacktracks < 1 || !(opt->TolFun > 0))
     return fail(OCS_ERR_INVALID, "bad options");
+  if (opt->algorithm != OCS_SS_SPG && opt->algorithm != OCS_SS_LBFGS)
+    return fail(OCS_ERR_INVALID, "algorithm %d: expected OCS_SS_SPG or OCS_SS_LBFGS", opt->algorithm);
+  const bool lbfgs = opt->algorithm == OCS_SS_LBFGS;
+  if (lbfgs && (opt->pairs < 1 || opt->pairs > 16)) return fail(OCS_ERR_INVALID, "pairs %d: expected 1..16", opt->pairs);
   hipStream_t s = (hipStream_t)stream;
   int nB = 0, nC = 0, nT = 0;
   OCS_TRY(ocs_control_dims(c, &nB, &nC, &nT));
@@ -88,9 +98,31 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
   a.accepted = fl + B;
   a.iters = fl + 2 * B;
   a.counter = (int*)counter.p;
+  // projected L-BFGS: the ring of (s, y) pairs of every instance, empty at the start
+  DevBuf ring, coef, lflags;
+  LbfgsArgs l;
+  if (lbfgs) {
+    const size_t m = (size_t)opt->pairs;
+    OCS_TRY(ring.ensure(2 * m * vb));
+    OCS_TRY(coef.ensure(sizeof(double) * 2 * m * B));
+    OCS_TRY(lflags.ensure(sizeof(int) * ((size_t)nV + 3) * B));
+    int* lf = (int*)lflags.p;
+    l.a = a;
+    l.pairs = opt->pairs;
+    l.S = ring.d();
+    l.Y = ring.d() + m * (size_t)nV * B;
+    l.rho = coef.d();
+    l.al = coef.d() + m * B;
+    l.head = lf;
+    l.count = lf + B;
+    l.qn = lf + 2 * B;
+    l.fr = lf + 3 * B;
+    HIP_TRY(hipMemsetAsync(lflags.p, 0, sizeof(int) * 3 * B, s));
+  }
   auto count_after = [&](int which, int it, int* n) -> int {
     HIP_TRY(hipMemsetAsync(counter.p, 0, sizeof(int), s));
-    LAUNCH_TRY(launch_spg(which, a, it, nullptr, nullptr, s));
+    if (lbfgs) LAUNCH_TRY(launch_lbfgs(which, l, s));
+    else LAUNCH_TRY(launch_spg(which, a, it, nullptr, nullptr, s));
     HIP_TRY(hipMemcpyAsync(n, counter.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return OCS_OK;
@@ -107,7 +139,8 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
       OCS_TRY(count_after(2, it, &nrejected));
       if (nrejected == 0) break;
     }
-    LAUNCH_TRY(launch_spg(3, a, it, nullptr, nullptr, s));
+    if (lbfgs) LAUNCH_TRY(launch_lbfgs(3, l, s));
+    else LAUNCH_TRY(launch_spg(3, a, it, nullptr, nullptr, s));
   }
   // x0 at FreeInitStates follows the last evaluated trial point: make it (and J, g) those of the returned v
   if (nFree > 0) OCS_TRY(ocs_nlp_objective_dev(g, p, c, batch, x0, v, nFree, FreeInitStates, J, a.g, stream));

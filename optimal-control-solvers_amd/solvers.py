@@ -251,7 +251,7 @@ def initial_v_batch(control, u0, bounds, B):
 
 def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrator=None, u0=0.0, TolX=1e-5,
                           TolFun=3e-4, MaxIter=500, memory=10, FreeInitStates=(), FreeStateBounds=None, v0=None,
-                          constraints="warn", maxBacktracks=None):
+                          constraints="warn", maxBacktracks=None, Algorithm="spg", pairs=None):
     """Batched direct single shooting: B independent NLPs  min_v J_b(v), Lb <= v <= Ub  --
     one per column of x0 and/or per per-trajectory parameter set of `prob` -- solved together on the GPU by the
     library's ocs_single_shooting_batch_dev.
@@ -264,13 +264,20 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     is the same KKT point.  Stopping (per instance): ||P(v - g) - v||_inf <= TolFun or step <= TolX.
     maxBacktracks: objective evaluations of one line search (default: that of ocs_ss_default_options); an instance
     whose line search runs out of them stops where it is.
+    Algorithm: "spg" (default) or "lbfgs" (case-insensitive; the reference's 'Algorithm' option, single_shooting.m:22):
+    a projected limited-memory BFGS per instance on the same evaluations, stopping tests and outputs -- coefficients on a
+    bound with the gradient pushing outward are held, the two-loop recursion over the last `pairs` (s, y) pairs (1..16,
+    default that of ocs_ss_default_options) gives the direction on the others, monotone Armijo search along the projected
+    path; SPG's direction while no pair is held.  `memory` belongs to SPG's line search and is not used by it.
     Free initial states ride at the tail of v, starting at x0 (single_shooting.m:81-85), inside FreeStateBounds
     (nFree x 2, :91-94; default unbounded).
     u0: nC values shared by the instances, or nC x B, a start per instance (each instance's own uStar, as
     tests/solve_test_problem.m:37 passes 'u0', uStar'); clamped to the bounds and expanded with compute_initial_v.
     Returns a dict of device tensors: v [nV(+nFree)][B], J [B], iterations [B], converged [B],
     projected_gradient [B], x0 [nS][B] and `soln_of(b)` (J, v and the control callable of instance b)."""
-    from ._lib import SsOptions
+    from ._lib import SS_ALGORITHMS, SsOptions
+    if not isinstance(Algorithm, str) or Algorithm.lower() not in SS_ALGORITHMS:
+        raise ValueError(f"Algorithm: expected one of {sorted(SS_ALGORITHMS)}, got {Algorithm!r}")
     tspan = _f(tspan).ravel()
     integrator = Integrator or RK4Integrator(tspan)
     nC = prob.ControlBounds.shape[0]
@@ -318,6 +325,9 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     o.TolX, o.TolFun, o.MaxIter, o.memory = float(TolX), float(TolFun), int(MaxIter), int(memory)
     if maxBacktracks is not None:
         o.maxBacktracks = int(maxBacktracks)
+    o.algorithm = SS_ALGORITHMS[Algorithm.lower()]
+    if pairs is not None:
+        o.pairs = int(pairs)
     rc = lib.ocs_single_shooting_batch_dev(integrator._h, prob._h, control._h, B, _dptr(x0d), _dptr(v), nFree, fis,
                                            _p(Lb), _p(Ub), C.byref(o), _dptr(J), C.c_void_p(iters.data_ptr()), C.c_void_p(conv.data_ptr()), _dptr(pgn),
                                            _stream())
