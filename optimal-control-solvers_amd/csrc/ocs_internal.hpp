@@ -293,10 +293,8 @@ struct SpgArgs {
   double *J, *Jt, *alpha, *lam, *gtd, *fmax;  // [B]
   double* hist;               // [memory][B] last objective values (non-monotone line search)
   int *active, *accepted, *iters;  // [B]
-  int* counter;               // instances still active (which = 1) / rejected by the line search (which = 2)
+  int* counter;               // instances still active (Direction) / rejected by the line search (Accept)
 };
-// which: 0 init, 1 stopping test + direction + first trial, 2 Armijo test + next trial, 3 take the step, 4 verdict
-int launch_spg(int which, const SpgArgs& a, int it, double* pgnorm, int* converged, hipStream_t s);
 // projected L-BFGS on the same state (alpha, the trial point and the flags are SPG's; hist and fmax are unused; gtd holds
 // g'(vt - v) of the current trial point): per-instance ring of (s, y) pairs
 struct LbfgsArgs {
@@ -307,9 +305,17 @@ struct LbfgsArgs {
   int *fr;            // [nV][B] free coefficients of the current iterate
   int *head, *count, *qn;  // [B] next slot, pairs held, the direction of this iteration is a quasi-Newton one
 };
-// which: 1 stopping test + active set + direction + first trial, 2 Armijo test + next trial, 3 take the step + pair store
-// (init and verdict are launch_spg's 0 and 4)
-int launch_lbfgs(int which, const LbfgsArgs& l, hipStream_t s);
+// the phases of one solve: first evaluation done; stopping test + direction + first trial point; Armijo test + next trial
+// point; take the step; verdict.  Init and Finish are common to both algorithms
+enum class SsPhase { Init, Direction, Accept, Update, Finish };
+struct ShootingArgs {
+  int algorithm;      // OCS_SS_SPG (l.a alone is filled) or OCS_SS_LBFGS
+  LbfgsArgs l;
+  int it;             // Update: the iteration in progress (SPG's slot in hist)
+  double* pgnorm;     // Finish: [B] or NULL, ||P(v - g) - v||_inf of the result
+  int* converged;     // Finish: [B] or NULL, its verdict
+};
+int launch_shooting(SsPhase phase, const ShootingArgs& r, hipStream_t s);
 int control_grid_parts(int N);
 // batched vectorInterpolant: V [n][nComp][B] -> out [nq][nComp][B]; method as OCS_INTERP_*; t: tables of the sample grid
 int launch_interp(int method, const FbsTables& t, int nComp, int nq, const int* KQ, const double* SQ, int batch,

@@ -12,10 +12,26 @@
 #include "ocs_trace.hpp"
 #include "ocs_handles.hpp"
 
+#include <initializer_list>
 #include <limits>
+#include <utility>
 #include <vector>
 
 using namespace ocs;
+
+// `fields` = (pointer to set, rows): [rows][B] arrays laid side by side in one device buffer, in this order
+template <class T>
+static int carve(DevBuf& buf, size_t B, std::initializer_list<std::pair<T**, size_t>> fields) {
+  size_t rows = 0;
+  for (const auto& f : fields) rows += f.second;
+  OCS_TRY(buf.ensure(sizeof(T) * rows * B));
+  T* at = (T*)buf.p;
+  for (const auto& f : fields) {
+    *f.first = at;
+    at += f.second * B;
+  }
+  return OCS_OK;
+}
 
 extern "C" {
 
@@ -45,23 +61,22 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
     return fail(OCS_ERR_INVALID, "bad options");
   if (opt->algorithm != OCS_SS_SPG && opt->algorithm != OCS_SS_LBFGS)
     return fail(OCS_ERR_INVALID, "algorithm %d: expected OCS_SS_SPG or OCS_SS_LBFGS", opt->algorithm);
-  const bool lbfgs = opt->algorithm == OCS_SS_LBFGS;
-  if (lbfgs && (opt->pairs < 1 || opt->pairs > 16)) return fail(OCS_ERR_INVALID, "pairs %d: expected 1..16", opt->pairs);
+  if (opt->algorithm == OCS_SS_LBFGS && (opt->pairs < 1 || opt->pairs > 16))
+    return fail(OCS_ERR_INVALID, "pairs %d: expected 1..16", opt->pairs);
   hipStream_t s = (hipStream_t)stream;
   int nB = 0, nC = 0, nT = 0;
   OCS_TRY(ocs_control_dims(c, &nB, &nC, &nT));
   const int nV = nB * nC + nFree;
   const size_t B = (size_t)batch, vb = sizeof(double) * (size_t)nV * B;
-  DevBuf gbuf, dbuf, vtbuf, gtbuf, sc, hist, flags, lbub, counter, conv;
+  DevBuf gbuf, dbuf, vtbuf, gtbuf, sc, hist, flags, lbub, counter, conv, ring, coef, lflags;
   OCS_TRY(gbuf.ensure(vb));
   OCS_TRY(dbuf.ensure(vb));
   OCS_TRY(vtbuf.ensure(vb));
   OCS_TRY(gtbuf.ensure(vb));
-  OCS_TRY(sc.ensure(sizeof(double) * 5 * B));  // Jt, alpha, lam, gtd, fmax
   OCS_TRY(hist.ensure(sizeof(double) * (size_t)opt->memory * B));
-  OCS_TRY(flags.ensure(sizeof(int) * 3 * B));  // active, accepted, iters
   OCS_TRY(lbub.ensure(sizeof(double) * 2 * (size_t)nV));
   OCS_TRY(counter.ensure(sizeof(int)));
+  OCS_TRY(conv.ensure(sizeof(int) * B));
   {
     std::vector<double> h(2 * (size_t)nV);
     const double inf = std::numeric_limits<double>::infinity();
@@ -73,8 +88,12 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
     HIP_TRY(hipMemcpyAsync(lbub.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
-  int* fl = (int*)flags.p;
-  SpgArgs a;
+  ShootingArgs r = {};
+  LbfgsArgs& l = r.l;
+  SpgArgs& a = l.a;
+  r.algorithm = opt->algorithm;
+  r.pgnorm = pgnorm;
+  r.converged = (int*)conv.p;
   a.batch = batch;
   a.nV = nV;
   a.memory = opt->memory;
@@ -88,64 +107,46 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
   a.vt = vtbuf.d();
   a.gt = gtbuf.d();
   a.J = J;
-  a.Jt = sc.d();
-  a.alpha = sc.d() + B;
-  a.lam = sc.d() + 2 * B;
-  a.gtd = sc.d() + 3 * B;
-  a.fmax = sc.d() + 4 * B;
   a.hist = hist.d();
-  a.active = fl;
-  a.accepted = fl + B;
-  a.iters = fl + 2 * B;
   a.counter = (int*)counter.p;
-  // projected L-BFGS: the ring of (s, y) pairs of every instance, empty at the start
-  DevBuf ring, coef, lflags;
-  LbfgsArgs l;
-  if (lbfgs) {
+  OCS_TRY(carve<double>(sc, B, {{&a.Jt, 1}, {&a.alpha, 1}, {&a.lam, 1}, {&a.gtd, 1}, {&a.fmax, 1}}));
+  OCS_TRY(carve<int>(flags, B, {{&a.active, 1}, {&a.accepted, 1}, {&a.iters, 1}}));
+  if (opt->algorithm == OCS_SS_LBFGS) {  // the ring of (s, y) pairs of every instance, empty at the start
     const size_t m = (size_t)opt->pairs;
-    OCS_TRY(ring.ensure(2 * m * vb));
-    OCS_TRY(coef.ensure(sizeof(double) * 2 * m * B));
-    OCS_TRY(lflags.ensure(sizeof(int) * ((size_t)nV + 3) * B));
-    int* lf = (int*)lflags.p;
-    l.a = a;
     l.pairs = opt->pairs;
-    l.S = ring.d();
-    l.Y = ring.d() + m * (size_t)nV * B;
-    l.rho = coef.d();
-    l.al = coef.d() + m * B;
-    l.head = lf;
-    l.count = lf + B;
-    l.qn = lf + 2 * B;
-    l.fr = lf + 3 * B;
-    HIP_TRY(hipMemsetAsync(lflags.p, 0, sizeof(int) * 3 * B, s));
+    OCS_TRY(carve<double>(ring, B, {{&l.S, m * nV}, {&l.Y, m * nV}}));
+    OCS_TRY(carve<double>(coef, B, {{&l.rho, m}, {&l.al, m}}));
+    OCS_TRY(carve<int>(lflags, B, {{&l.head, 1}, {&l.count, 1}, {&l.qn, 1}, {&l.fr, (size_t)nV}}));
+    HIP_TRY(hipMemsetAsync(l.head, 0, sizeof(int) * (size_t)(l.fr - l.head), s));  // head, count, qn
   }
-  auto count_after = [&](int which, int it, int* n) -> int {
+  auto launch = [&](SsPhase phase) -> int {
+    LAUNCH_TRY(launch_shooting(phase, r, s));
+    return OCS_OK;
+  };
+  auto count_after = [&](SsPhase phase, int* n) -> int {  // the instances the phase counted (SpgArgs.counter)
     HIP_TRY(hipMemsetAsync(counter.p, 0, sizeof(int), s));
-    if (lbfgs) LAUNCH_TRY(launch_lbfgs(which, l, s));
-    else LAUNCH_TRY(launch_spg(which, a, it, nullptr, nullptr, s));
+    OCS_TRY(launch(phase));
     HIP_TRY(hipMemcpyAsync(n, counter.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return OCS_OK;
   };
   OCS_TRY(ocs_nlp_objective_dev(g, p, c, batch, x0, v, nFree, FreeInitStates, J, a.g, stream));
-  LAUNCH_TRY(launch_spg(0, a, 0, nullptr, nullptr, s));
-  for (int it = 0; it < opt->MaxIter; ++it) {
+  OCS_TRY(launch(SsPhase::Init));
+  for (r.it = 0; r.it < opt->MaxIter; ++r.it) {
     int nactive = 0;
-    OCS_TRY(count_after(1, it, &nactive));  // stopping test + direction + first trial point
+    OCS_TRY(count_after(SsPhase::Direction, &nactive));
     if (nactive == 0) break;
     for (int ls = 0; ls < opt->maxBacktracks; ++ls) {
       OCS_TRY(ocs_nlp_objective_dev(g, p, c, batch, x0, a.vt, nFree, FreeInitStates, a.Jt, a.gt, stream));
       int nrejected = 0;
-      OCS_TRY(count_after(2, it, &nrejected));
+      OCS_TRY(count_after(SsPhase::Accept, &nrejected));
       if (nrejected == 0) break;
     }
-    if (lbfgs) LAUNCH_TRY(launch_lbfgs(3, l, s));
-    else LAUNCH_TRY(launch_spg(3, a, it, nullptr, nullptr, s));
+    OCS_TRY(launch(SsPhase::Update));
   }
   // x0 at FreeInitStates follows the last evaluated trial point: make it (and J, g) those of the returned v
   if (nFree > 0) OCS_TRY(ocs_nlp_objective_dev(g, p, c, batch, x0, v, nFree, FreeInitStates, J, a.g, stream));
-  OCS_TRY(conv.ensure(sizeof(int) * B));
-  LAUNCH_TRY(launch_spg(4, a, 0, pgnorm, (int*)conv.p, s));
+  OCS_TRY(launch(SsPhase::Finish));
   std::vector<int> hc(B);
   HIP_TRY(hipMemcpyAsync(hc.data(), conv.p, sizeof(int) * B, hipMemcpyDeviceToHost, s));
   if (converged) HIP_TRY(hipMemcpyAsync(converged, conv.p, sizeof(int) * B, hipMemcpyDeviceToDevice, s));

@@ -5,57 +5,114 @@
 // [rows][B] so that a wave reads consecutive instances.
 #include "ocs_device_common.hpp"
 #include "ocs_internal.hpp"
+#include "../../include/ocs.h"
 
 namespace ocs {
 
+// ---- the pieces both algorithms are made of, each over (args, instance b), every loop row after row
 
-__device__ static inline double spg_proj(double w, double lb, double ub) { return fmin(fmax(w, lb), ub); }
+// projection of coefficient i on its bounds
+__device__ static inline double proj(const SpgArgs& a, int i, double w) { return fmin(fmax(w, a.lb[i]), a.ub[i]); }
+
+// ||P(v - g) - v||_inf
+__device__ static inline double pg_norm(const SpgArgs& a, int b) {
+  const size_t B = (size_t)a.batch;
+  double pgn = 0.0;
+  for (int i = 0; i < a.nV; ++i) {
+    const double v = a.v[i * B + b], g = a.g[i * B + b];
+    pgn = fmax(pgn, fabs(proj(a, i, v - g) - v));
+  }
+  return pgn;
+}
+
+// stopping test: whether the instance goes on (a NaN norm stops it too)
+__device__ static inline bool goes_on(const SpgArgs& a, int b) {
+  const size_t B = (size_t)a.batch;
+  int act = a.active[b];
+  if (act) {
+    if (!(pg_norm(a, b) > a.TolFun)) act = 0;
+    a.active[b] = act;
+  }
+  if (!act) {  // finished: its trial point stays its solution, so that the batch evaluation leaves it alone
+    a.accepted[b] = 1;
+    for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = a.v[i * B + b];
+  }
+  return act;
+}
+
+// SPG's direction d = P(v - alpha g) - v with its first trial point; returns g'd.  SPG takes vt = P(v + d): v + (lb - v)
+// can round to one ulp outside the box.  L-BFGS (on_bound) takes the projection itself, so that a coefficient that
+// reaches a bound is on it exactly (its active set tests equality)
+__device__ static inline double spg_direction(const SpgArgs& a, int b, bool on_bound) {
+  const size_t B = (size_t)a.batch;
+  const double alpha = a.alpha[b];
+  double gtd = 0.0;
+  for (int i = 0; i < a.nV; ++i) {
+    const double v = a.v[i * B + b], g = a.g[i * B + b], w = proj(a, i, v - alpha * g);
+    const double d = w - v;
+    a.d[i * B + b] = d;
+    a.vt[i * B + b] = on_bound ? w : proj(a, i, v + d);
+    gtd += g * d;
+  }
+  return gtd;
+}
+
+// a rejected trial point: half the step, vt = P(v + lam d)
+__device__ static inline void halve_step(const SpgArgs& a, int b) {
+  const size_t B = (size_t)a.batch;
+  const double half = 0.5 * a.lam[b];
+  a.lam[b] = half;
+  for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = proj(a, i, a.v[i * B + b] + half * a.d[i * B + b]);
+}
+
+// the accepted step: one pass over s = vt - v, y = gt - g with s'y, s's and max |s|; `row(i, s, y)` is what the algorithm
+// adds to a row; with `take` the pass moves v, g to the accepted point
+struct StepSums { double sty, sts, smax; };
+template <class Row>
+__device__ static inline StepSums step_rows(const SpgArgs& a, int b, bool take, Row row) {
+  const size_t B = (size_t)a.batch;
+  StepSums r = {0.0, 0.0, 0.0};
+  for (int i = 0; i < a.nV; ++i) {
+    const double vn = a.vt[i * B + b], gn = a.gt[i * B + b];
+    const double s = vn - a.v[i * B + b], y = gn - a.g[i * B + b];
+    r.sty += s * y;
+    r.sts += s * s;
+    r.smax = fmax(r.smax, fabs(s));
+    row(i, s, y);
+    if (take) {
+      a.v[i * B + b] = vn;
+      a.g[i * B + b] = gn;
+    }
+  }
+  return r;
+}
+// and what follows it: the objective, the Barzilai-Borwein step length of the next iteration, the stop on a small step
+__device__ static inline void step_taken(const SpgArgs& a, int b, const StepSums& r) {
+  a.J[b] = a.Jt[b];
+  const double an = r.sty > 0.0 ? r.sts / fmax(r.sty, 1e-300) : 1e3;
+  a.alpha[b] = fmin(fmax(an, 1e-10), 1e10);
+  if (r.smax <= a.TolX) a.active[b] = 0;
+}
+
+// ---- spectral projected gradient
 
 // first evaluation done: step length 1 / ||P(v - g) - v||_inf, objective history filled with J
 __global__ __launch_bounds__(256) void k_spg_init(SpgArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.batch) return;
   const size_t B = (size_t)a.batch;
-  double pgn = 0.0;
-  for (int i = 0; i < a.nV; ++i) {
-    const double v = a.v[i * B + b], g = a.g[i * B + b];
-    pgn = fmax(pgn, fabs(spg_proj(v - g, a.lb[i], a.ub[i]) - v));
-  }
-  a.alpha[b] = 1.0 / fmax(pgn, 1e-12);
+  a.alpha[b] = 1.0 / fmax(pg_norm(a, b), 1e-12);
   for (int m = 0; m < a.memory; ++m) a.hist[m * B + b] = a.J[b];
   a.active[b] = 1;
   a.iters[b] = 0;
 }
 
-// stopping test, search direction d = P(v - alpha g) - v, g'd, the non-monotone reference value, first trial point
+// stopping test, search direction, g'd, the non-monotone reference value, first trial point
 __global__ __launch_bounds__(256) void k_spg_direction(SpgArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
+  if (b >= a.batch || !goes_on(a, b)) return;
   const size_t B = (size_t)a.batch;
-  int act = a.active[b];
-  if (act) {
-    double pgn = 0.0;
-    for (int i = 0; i < a.nV; ++i) {
-      const double v = a.v[i * B + b], g = a.g[i * B + b];
-      pgn = fmax(pgn, fabs(spg_proj(v - g, a.lb[i], a.ub[i]) - v));
-    }
-    if (!(pgn > a.TolFun)) act = 0;
-    a.active[b] = act;
-  }
-  if (!act) {  // finished: its trial point stays its solution, so that the batch evaluation leaves it alone
-    a.accepted[b] = 1;
-    for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = a.v[i * B + b];
-    return;
-  }
-  const double alpha = a.alpha[b];
-  double gtd = 0.0;
-  for (int i = 0; i < a.nV; ++i) {
-    const double v = a.v[i * B + b], g = a.g[i * B + b];
-    const double d = spg_proj(v - alpha * g, a.lb[i], a.ub[i]) - v;
-    a.d[i * B + b] = d;
-    a.vt[i * B + b] = spg_proj(v + d, a.lb[i], a.ub[i]);  // v + (lb - v) can round to one ulp outside the box
-    gtd += g * d;
-  }
+  const double gtd = spg_direction(a, b, false);
   double fmx = a.hist[b];
   for (int m = 1; m < a.memory; ++m) fmx = fmax(fmx, a.hist[m * B + b]);
   a.gtd[b] = gtd;
@@ -70,83 +127,44 @@ __global__ __launch_bounds__(256) void k_spg_direction(SpgArgs a) {
 __global__ __launch_bounds__(256) void k_spg_accept(SpgArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.batch || a.accepted[b]) return;
-  const size_t B = (size_t)a.batch;
-  const double lam = a.lam[b];
-  if (a.Jt[b] <= a.fmax[b] + 1e-4 * lam * a.gtd[b]) {
+  if (a.Jt[b] <= a.fmax[b] + 1e-4 * a.lam[b] * a.gtd[b]) {
     a.accepted[b] = 2;  // accepted in this iteration
     return;
   }
-  const double half = 0.5 * lam;
-  a.lam[b] = half;
-  for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = spg_proj(a.v[i * B + b] + half * a.d[i * B + b], a.lb[i], a.ub[i]);
+  halve_step(a, b);
   atomicAdd(a.counter, 1);
 }
 
-// take the accepted point, Barzilai-Borwein step length for the next iteration, history, stopping on a small step
+// take the accepted point (a failed line search stops the instance where it is), history slot of iteration it
 __global__ __launch_bounds__(256) void k_spg_update(SpgArgs a, int it) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.batch) return;
   const size_t B = (size_t)a.batch;
   if (a.active[b]) {
     a.iters[b] += 1;
-    if (a.accepted[b] == 2) {
-      double sty = 0.0, sts = 0.0, smax = 0.0;
-      for (int i = 0; i < a.nV; ++i) {
-        const double vn = a.vt[i * B + b], gn = a.gt[i * B + b];
-        const double s = vn - a.v[i * B + b], y = gn - a.g[i * B + b];
-        sty += s * y;
-        sts += s * s;
-        smax = fmax(smax, fabs(s));
-        a.v[i * B + b] = vn;
-        a.g[i * B + b] = gn;
-      }
-      a.J[b] = a.Jt[b];
-      const double an = sty > 0.0 ? sts / fmax(sty, 1e-300) : 1e3;
-      a.alpha[b] = fmin(fmax(an, 1e-10), 1e10);
-      if (smax <= a.TolX) a.active[b] = 0;
-    } else {
-      a.active[b] = 0;  // the line search failed: the instance stops where it is
-    }
+    if (a.accepted[b] == 2) step_taken(a, b, step_rows(a, b, true, [](int, double, double) {}));
+    else a.active[b] = 0;
   }
   a.hist[(size_t)(it % a.memory) * B + b] = a.J[b];
 }
 
-// ||P(v - g) - v||_inf of the result and the verdict
+// ||P(v - g) - v||_inf of the result and the verdict (both algorithms)
 __global__ __launch_bounds__(256) void k_spg_finish(SpgArgs a, double* pgnorm, int* converged) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.batch) return;
-  const size_t B = (size_t)a.batch;
-  double pgn = 0.0;
-  for (int i = 0; i < a.nV; ++i) {
-    const double v = a.v[i * B + b], g = a.g[i * B + b];
-    pgn = fmax(pgn, fabs(spg_proj(v - g, a.lb[i], a.ub[i]) - v));
-  }
+  const double pgn = pg_norm(a, b);
   if (pgnorm) pgnorm[b] = pgn;
   if (converged) converged[b] = pgn <= 10.0 * a.TolFun;
 }
 
-int launch_spg(int which, const SpgArgs& a, int it, double* pgnorm, int* converged, hipStream_t s) {
-  const dim3 grid((a.batch + 255) / 256), block(256);
-  switch (which) {
-    case 0: k_spg_init<<<grid, block, 0, s>>>(a); break;
-    case 1: k_spg_direction<<<grid, block, 0, s>>>(a); break;
-    case 2: k_spg_accept<<<grid, block, 0, s>>>(a); break;
-    case 3: k_spg_update<<<grid, block, 0, s>>>(a, it); break;
-    case 4: k_spg_finish<<<grid, block, 0, s>>>(a, pgnorm, converged); break;
-    default: return -1;
-  }
-  return hip_rc(hipGetLastError());
-}
-
-// ---- projected L-BFGS (ocs_ss_options.algorithm = OCS_SS_LBFGS): the same phases as SPG, one fused launch each.
-// k_spg_init and k_spg_finish are shared; the iteration is specified statement by statement in tests/lbfgs_twin.py.
+// ---- projected L-BFGS (ocs_ss_options.algorithm = OCS_SS_LBFGS): the same phases, one fused launch each; init and
+// verdict are SPG's.  The iteration is specified statement by statement in tests/lbfgs_twin.py.
 
 // slot of the j-th newest pair in the ring (j = 0 the newest)
 __device__ static inline int lbfgs_slot(int head, int pairs, int j) { return (head + pairs - 1 - j) % pairs; }
 
-// g'(vt - v) of the current trial point, row after row
-__device__ static inline double lbfgs_gts(const LbfgsArgs& l, int b) {
-  const SpgArgs& a = l.a;
+// g'(vt - v) of the current trial point
+__device__ static inline double lbfgs_gts(const SpgArgs& a, int b) {
   const size_t B = (size_t)a.batch;
   double gts = 0.0;
   for (int i = 0; i < a.nV; ++i) gts += a.g[i * B + b] * (a.vt[i * B + b] - a.v[i * B + b]);
@@ -158,23 +176,8 @@ __device__ static inline double lbfgs_gts(const LbfgsArgs& l, int b) {
 __global__ __launch_bounds__(256) void k_lbfgs_direction(LbfgsArgs l) {
   const SpgArgs& a = l.a;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
+  if (b >= a.batch || !goes_on(a, b)) return;
   const size_t B = (size_t)a.batch, nVB = (size_t)a.nV * B;
-  int act = a.active[b];
-  if (act) {
-    double pgn = 0.0;
-    for (int i = 0; i < a.nV; ++i) {
-      const double v = a.v[i * B + b], g = a.g[i * B + b];
-      pgn = fmax(pgn, fabs(spg_proj(v - g, a.lb[i], a.ub[i]) - v));
-    }
-    if (!(pgn > a.TolFun)) act = 0;
-    a.active[b] = act;
-  }
-  if (!act) {  // finished: its trial point stays its solution, so that the batch evaluation leaves it alone
-    a.accepted[b] = 1;
-    for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = a.v[i * B + b];
-    return;
-  }
   const int pairs = l.pairs, head = l.head[b];
   int cnt = l.count[b];
   int qn = cnt > 0;
@@ -221,22 +224,15 @@ __global__ __launch_bounds__(256) void k_lbfgs_direction(LbfgsArgs l) {
       gtd += a.g[i * B + b] * d;
     }
     if (gtd < 0.0 && gtd >= -1.7976931348623157e308) {
-      for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = spg_proj(a.v[i * B + b] + a.d[i * B + b], a.lb[i], a.ub[i]);
+      for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = proj(a, i, a.v[i * B + b] + a.d[i * B + b]);
     } else {  // not a finite descent direction: drop the pairs
       qn = 0;
       l.count[b] = 0;
     }
   }
-  if (!qn) {  // the trial point is the projection itself: a coefficient that reaches a bound is on it exactly
-    const double alpha = a.alpha[b];
-    for (int i = 0; i < a.nV; ++i) {
-      const double v = a.v[i * B + b], w = spg_proj(v - alpha * a.g[i * B + b], a.lb[i], a.ub[i]);
-      a.d[i * B + b] = w - v;
-      a.vt[i * B + b] = w;
-    }
-  }
+  if (!qn) spg_direction(a, b, true);
   l.qn[b] = qn;
-  a.gtd[b] = lbfgs_gts(l, b);
+  a.gtd[b] = lbfgs_gts(a, b);
   a.lam[b] = 1.0;
   a.accepted[b] = 0;
   atomicAdd(a.counter, 1);
@@ -247,21 +243,19 @@ __global__ __launch_bounds__(256) void k_lbfgs_accept(LbfgsArgs l) {
   const SpgArgs& a = l.a;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.batch || a.accepted[b]) return;
-  const size_t B = (size_t)a.batch;
   const double gts = a.gtd[b];
   if (gts < 0.0 && a.Jt[b] <= a.J[b] + 1e-4 * gts) {
     a.accepted[b] = 2;  // accepted in this iteration
     return;
   }
-  const double half = 0.5 * a.lam[b];
-  a.lam[b] = half;
-  for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = spg_proj(a.v[i * B + b] + half * a.d[i * B + b], a.lb[i], a.ub[i]);
-  a.gtd[b] = lbfgs_gts(l, b);
+  halve_step(a, b);
+  a.gtd[b] = lbfgs_gts(a, b);
   atomicAdd(a.counter, 1);
 }
 
-// take the accepted point, Barzilai-Borwein step length as in SPG, store the pair if s'y > 2.2e-16 y'y; a line search
-// that failed on a quasi-Newton direction drops the pairs and goes on, one that failed on SPG's direction stops
+// take the accepted point and store the pair if s'y > 2.2e-16 y'y; a line search that failed on a quasi-Newton direction
+// drops the pairs and goes on, one that failed on SPG's direction stops.  Two passes of step_rows: slot `head` may hold
+// the oldest pair, which stays in use unless the sums of the whole step let the new one in
 __global__ __launch_bounds__(256) void k_lbfgs_update(LbfgsArgs l) {
   const SpgArgs& a = l.a;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -273,43 +267,44 @@ __global__ __launch_bounds__(256) void k_lbfgs_update(LbfgsArgs l) {
     else a.active[b] = 0;
     return;
   }
-  double sty = 0.0, sts = 0.0, yty = 0.0, smax = 0.0;
-  for (int i = 0; i < a.nV; ++i) {
-    const double s = a.vt[i * B + b] - a.v[i * B + b], y = a.gt[i * B + b] - a.g[i * B + b];
-    sty += s * y;
-    sts += s * s;
-    yty += y * y;
-    smax = fmax(smax, fabs(s));
-  }
-  const int store = sty > 2.2e-16 * yty, head = l.head[b];
+  double yty = 0.0;
+  const StepSums r = step_rows(a, b, false, [&](int, double, double y) { yty += y * y; });
+  const int store = r.sty > 2.2e-16 * yty, head = l.head[b];
   double *S = l.S + (size_t)head * nVB, *Y = l.Y + (size_t)head * nVB;
-  for (int i = 0; i < a.nV; ++i) {
-    const double vn = a.vt[i * B + b], gn = a.gt[i * B + b];
+  step_rows(a, b, true, [&](int i, double s, double y) {
     if (store) {
-      S[i * B + b] = vn - a.v[i * B + b];
-      Y[i * B + b] = gn - a.g[i * B + b];
+      S[i * B + b] = s;
+      Y[i * B + b] = y;
     }
-    a.v[i * B + b] = vn;
-    a.g[i * B + b] = gn;
-  }
+  });
   if (store) {
-    l.rho[(size_t)head * B + b] = 1.0 / sty;
+    l.rho[(size_t)head * B + b] = 1.0 / r.sty;
     l.head[b] = (head + 1) % l.pairs;
     l.count[b] = min(l.count[b] + 1, l.pairs);
   }
-  a.J[b] = a.Jt[b];
-  const double an = sty > 0.0 ? sts / fmax(sty, 1e-300) : 1e3;
-  a.alpha[b] = fmin(fmax(an, 1e-10), 1e10);
-  if (smax <= a.TolX) a.active[b] = 0;
+  step_taken(a, b, r);
 }
 
-int launch_lbfgs(int which, const LbfgsArgs& l, hipStream_t s) {
-  const dim3 grid((l.a.batch + 255) / 256), block(256);
-  switch (which) {
-    case 1: k_lbfgs_direction<<<grid, block, 0, s>>>(l); break;
-    case 2: k_lbfgs_accept<<<grid, block, 0, s>>>(l); break;
-    case 3: k_lbfgs_update<<<grid, block, 0, s>>>(l); break;
-    default: return -1;
+int launch_shooting(SsPhase phase, const ShootingArgs& r, hipStream_t s) {
+  const LbfgsArgs& l = r.l;
+  const SpgArgs& a = l.a;
+  const dim3 grid((a.batch + 255) / 256), block(256);
+  const bool lbfgs = r.algorithm == OCS_SS_LBFGS;
+  switch (phase) {
+    case SsPhase::Init: k_spg_init<<<grid, block, 0, s>>>(a); break;
+    case SsPhase::Direction:
+      if (lbfgs) k_lbfgs_direction<<<grid, block, 0, s>>>(l);
+      else k_spg_direction<<<grid, block, 0, s>>>(a);
+      break;
+    case SsPhase::Accept:
+      if (lbfgs) k_lbfgs_accept<<<grid, block, 0, s>>>(l);
+      else k_spg_accept<<<grid, block, 0, s>>>(a);
+      break;
+    case SsPhase::Update:
+      if (lbfgs) k_lbfgs_update<<<grid, block, 0, s>>>(l);
+      else k_spg_update<<<grid, block, 0, s>>>(a, r.it);
+      break;
+    case SsPhase::Finish: k_spg_finish<<<grid, block, 0, s>>>(a, r.pgnorm, r.converged); break;
   }
   return hip_rc(hipGetLastError());
 }

@@ -21,194 +21,119 @@ specification of the iteration; where the outline left a choice the choice is ma
   * the first trial point on SPG's direction is P(v - alpha g) itself, so a coefficient that reaches a bound is on it
     exactly and the equality tests of the active set mean what they say.
   * `memory` (SPG's non-monotone history) has no meaning here: the line search is monotone."""
-from types import SimpleNamespace
-
 import numpy as np
 
-from tests.spg_twin import _dot, _pgn, _proj, _rel
+from tests.spg_twin import (INDECISIVE_CAP, _dot, _proj, _rel, decide, decide_sign, goes_on, halve_step, make_inputs, note,
+                            run_twin, take_step)
 
 EPS_PAIR = 2.2e-16
-
-
-def _dotf(a, b, fr):                                    # running sum over the free rows only, row after row
-    s = np.zeros(a.shape[1])
-    for i in range(a.shape[0]):
-        s = s + np.where(fr[i], a[i] * b[i], 0.0)
-    return s
 
 
 def _col(A, slot):                                      # A [pairs][...][B], slot [B] -> A[slot[b], ..., b]
     return np.take_along_axis(A, slot.reshape((1,) * (A.ndim - 1) + (-1,)), axis=0)[0]
 
 
+def _lands(st, who, w):     # trial point P(w): a coefficient that moves and lands next to a bound decides whether it is on it
+    near = np.minimum(_rel(w, st.lb[:, None]), _rel(w, st.ub[:, None]))
+    near = np.where((st.lam * st.d != 0.0) & np.isfinite(w), near, np.inf).min(axis=0)
+    note(st, "lands on a bound", who, near)
+
+
+def _lbfgs_start(st):                                   # the pair rings are empty
+    nV, B = st.v.shape
+    st.S, st.Y = np.zeros((st.pairs, nV, B)), np.zeros((st.pairs, nV, B))
+    st.rho = np.zeros((st.pairs, B))
+    st.head, st.count = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+
+
+def _lbfgs_direction(st):                               # k_lbfgs_direction
+    v, g, lb, ub, pairs, head = st.v, st.g, st.lb, st.ub, st.pairs, st.head
+    goes_on(st)
+    # active set: on a bound with the gradient pushing outward
+    onl, onu = v == lb[:, None], v == ub[:, None]
+    fr = ~((onl & (g > 0.0)) | (onu & (g < 0.0)))
+    gmax = np.fmax.reduce(np.abs(g), axis=0, initial=0.0)
+    decide_sign(st, "active set", st.active, np.where(onl | onu, np.abs(g), np.inf).min(axis=0), gmax)
+    # two-loop recursion on the free coefficients, newest pair first (lbfgs_slot)
+    qn = st.active & (st.count > 0)
+    q = np.where(fr, g, 0.0)
+    al = np.zeros((pairs, v.shape[1]))
+    for j in range(pairs):
+        use = qn & (j < st.count)
+        slot = (head + pairs - 1 - j) % pairs
+        sj, yj = _col(st.S, slot), _col(st.Y, slot)
+        a = _col(st.rho, slot) * _dot(sj, q, fr)
+        al[j] = a
+        q = np.where(use & fr, q - a * yj, q)
+    slot = (head + pairs - 1) % pairs
+    s0, y0 = _col(st.S, slot), _col(st.Y, slot)
+    gamma = _dot(s0, y0, fr) / _dot(y0, y0, fr)
+    r = gamma * q
+    for j in range(pairs - 1, -1, -1):
+        use = qn & (j < st.count)
+        slot = (head + pairs - 1 - j) % pairs
+        sj, yj = _col(st.S, slot), _col(st.Y, slot)
+        beta = _col(st.rho, slot) * _dot(yj, r, fr)
+        r = np.where(use & fr, r + sj * (al[j] - beta), r)
+    dq = st.bump(np.where(fr, -r, 0.0))
+    dq = np.where(fr, dq, 0.0)                          # the probe leaves the zeros of the active set alone
+    gtd = _dot(g, dq)
+    # safeguard: not a finite descent direction -> drop the pairs, SPG's direction
+    decide_sign(st, "g'd < 0", qn, gtd, _dot(np.abs(g), np.abs(dq)))
+    st.reset = qn & ~((gtd < 0.0) & np.isfinite(gtd))
+    st.count = np.where(st.reset, 0, st.count)
+    st.qn = qn & ~st.reset
+    ds = st.bump(_proj(v - st.alpha * g, lb, ub) - v)   # spg_direction
+    st.d = np.where(st.active, np.where(st.qn, dq, ds), 0.0)
+    st.lam = np.ones(v.shape[1])
+    w = np.where(st.qn, v + st.d, v - st.alpha * g)     # spg_direction, L-BFGS's form: the projection itself (see above)
+    st.vt = np.where(st.active, _proj(w, lb, ub), v)    # a finished instance's trial point is its v
+    _lands(st, st.active, w)
+    st.gts = _dot(g, st.vt - v)                         # lbfgs_gts
+
+
+def _lbfgs_accept(st, pending):                         # k_lbfgs_accept
+    rhs = st.J + 1e-4 * st.gts
+    decide_sign(st, "g'(vt - v) < 0", pending, st.gts, _dot(np.abs(st.g), np.abs(st.vt - st.v)))
+    decide(st, "Armijo", pending & (st.gts < 0.0), st.Jt, rhs)
+    ok = pending & (st.gts < 0.0) & (st.Jt <= rhs)      # a NaN Jt is a rejection
+    rej = pending & ~ok
+    halve_step(st, rej)
+    _lands(st, rej, st.v + st.lam * st.d)
+    st.gts = np.where(rej, _dot(st.g, st.vt - st.v), st.gts)
+    return ok, rhs
+
+
+def _lbfgs_update(st, started):                         # k_lbfgs_update
+    pairs, head, qn = st.pairs, st.head, st.qn
+    st.iters += st.active
+    take = st.active & (st.accepted == 2)
+    s, y, sty, tolx = take_step(st, take)
+    yty = _dot(y, y)                                    # step_rows' first pass, with y'y
+    decide(st, "pair stored", take, sty, EPS_PAIR * yty)
+    store = take & (sty > EPS_PAIR * yty)               # a NaN fails the test
+    at = (head[None, None, :] == np.arange(pairs)[:, None, None]) & store[None, None, :]
+    st.S = np.where(at, s[None], st.S)
+    st.Y = np.where(at, y[None], st.Y)
+    st.rho = np.where(at[:, 0, :], (1.0 / sty)[None], st.rho)
+    st.head = np.where(store, (head + 1) % pairs, head)
+    st.count = np.where(store, np.minimum(st.count + 1, pairs), st.count)
+    failed = started & ~take
+    st.count = np.where(failed & qn, 0, st.count)       # a failed search on a quasi-Newton direction: drop the pairs, go on
+    st.active = (take & ~tolx) | (failed & qn)          # on SPG's direction the instance stops where it is
+    return take, tolx, dict(qn=qn.copy(), reset=st.reset, stored=store, skipped=take & ~store, sty=sty, count=st.count.copy())
+
+
 def lbfgs_twin(evaluate, v0, Lb, Ub, TolX, TolFun, MaxIter, maxBacktracks, pairs=8, memory=None, ulp_seed=None):
     """evaluate(V [nV][B]) -> (J [B], G [nV][B]), always called on the whole batch.  With `ulp_seed` every computed
     direction d and step length alpha is moved by one ulp in a seeded random direction.  Returns what spg_twin returns
-    (v, J, iterations, converged, pgn, backtracks, margin, active, snap, steps); a step record has in addition qn (the
-    direction was a quasi-Newton one), reset (the safeguard dropped the pairs), stored / skipped (the pair of an accepted
-    step was stored / failed its test), sty, count (pairs held after the iteration)."""
-    v = np.array(v0, dtype=np.float64, copy=True)
-    nV, B = v.shape
-    lb = np.full(nV, -np.inf) if Lb is None else np.asarray(Lb, dtype=np.float64).ravel()
-    ub = np.full(nV, np.inf) if Ub is None else np.asarray(Ub, dtype=np.float64).ravel()
-    rng = None if ulp_seed is None else np.random.default_rng(ulp_seed)
-
-    def bump(x):
-        if rng is None:
-            return x
-        return np.nextafter(x, np.where(rng.integers(0, 2, size=x.shape) == 1, np.inf, -np.inf))
-
-    margin = np.full(B, np.inf)
-    margins = {}                                        # the same per kind of decision (for the reader of a failing case)
-
-    def note(what, mask, r):
-        margin[mask] = np.minimum(margin, r)[mask]
-        m = margins.setdefault(what, np.full(B, np.inf))
-        m[mask] = np.minimum(m, r)[mask]
-
-    def decide(what, mask, a, b):                       # the instances of `mask` take the comparison a ? b
-        note(what, mask, _rel(a, b))
-
-    def decide_sign(what, mask, value, scale):          # the sign of `value`, measured on the scale of its terms
-        r = np.abs(value) / np.fmax(scale, 1e-300)
-        note(what, mask, np.where(np.isnan(r), np.inf, r))
-
-    def trial(lam, d, who, vt_old, full_spg):
-        """vt = P(v + lam d) for the instances `who`; a coefficient that moves and lands next to a bound decides whether
-        it is on it (active-set membership of the next iterate).  SPG's full step is P(v - alpha g) itself, not
-        P(v + d): v + ((ub - v) rounded) can end one ulp inside the box, and the active set asks for equality"""
-        w = np.where(full_spg, v - alpha * g, v + lam * d)
-        vt = _proj(w, lb, ub)
-        near = np.minimum(_rel(w, lb[:, None]), _rel(w, ub[:, None]))
-        near = np.where((lam * d != 0.0) & np.isfinite(w), near, np.inf).min(axis=0)
-        note("lands on a bound", who, near)
-        return np.where(who, vt, vt_old)
-
-    snap, steps = [], []
-
-    def snapshot():                                     # k_spg_finish
-        pgn = _pgn(v, g, lb, ub)
-        snap.append(SimpleNamespace(v=v.copy(), J=J.copy(), iterations=iters.copy(), active=active.copy(), pgn=pgn,
-                                    converged=pgn <= 10.0 * TolFun,
-                                    margin=np.minimum(margin, _rel(pgn, 10.0 * TolFun))))
-
-    with np.errstate(all="ignore"):
-        J, g = evaluate(v)
-        J, g = np.array(J, dtype=np.float64), np.array(g, dtype=np.float64)
-        # k_spg_init: the first step length; the pair rings are empty
-        alpha = bump(1.0 / np.fmax(_pgn(v, g, lb, ub), 1e-12))
-        active = np.ones(B, dtype=bool)
-        iters = np.zeros(B, dtype=np.int64)
-        S, Y = np.zeros((pairs, nV, B)), np.zeros((pairs, nV, B))
-        rho = np.zeros((pairs, B))
-        head, count = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
-        snapshot()
-        for it in range(MaxIter):
-            # k_lbfgs_direction: stopping test
-            pgn = _pgn(v, g, lb, ub)
-            decide("pgn <= TolFun", active, pgn, TolFun)
-            active = active & (pgn > TolFun)
-            accepted = np.where(active, 0, 1)
-            # active set: on a bound with the gradient pushing outward
-            onl, onu = v == lb[:, None], v == ub[:, None]
-            fr = ~((onl & (g > 0.0)) | (onu & (g < 0.0)))
-            gmax = np.fmax.reduce(np.abs(g), axis=0, initial=0.0)
-            decide_sign("active set", active, np.where(onl | onu, np.abs(g), np.inf).min(axis=0), gmax)
-            # two-loop recursion on the free coefficients, newest pair first
-            qn = active & (count > 0)
-            q = np.where(fr, g, 0.0)
-            al = np.zeros((pairs, B))
-            for j in range(pairs):
-                use = qn & (j < count)
-                slot = (head + pairs - 1 - j) % pairs
-                sj, yj = _col(S, slot), _col(Y, slot)
-                a = _col(rho, slot) * _dotf(sj, q, fr)
-                al[j] = a
-                q = np.where(use & fr, q - a * yj, q)
-            slot = (head + pairs - 1) % pairs
-            s0, y0 = _col(S, slot), _col(Y, slot)
-            gamma = _dotf(s0, y0, fr) / _dotf(y0, y0, fr)
-            r = gamma * q
-            for j in range(pairs - 1, -1, -1):
-                use = qn & (j < count)
-                slot = (head + pairs - 1 - j) % pairs
-                sj, yj = _col(S, slot), _col(Y, slot)
-                beta = _col(rho, slot) * _dotf(yj, r, fr)
-                r = np.where(use & fr, r + sj * (al[j] - beta), r)
-            dq = bump(np.where(fr, -r, 0.0))
-            dq = np.where(fr, dq, 0.0)                  # the probe leaves the zeros of the active set alone
-            gtd = _dot(g, dq)
-            # safeguard: not a finite descent direction -> drop the pairs, SPG's direction
-            decide_sign("g'd < 0", qn, gtd, _dot(np.abs(g), np.abs(dq)))
-            reset = qn & ~((gtd < 0.0) & np.isfinite(gtd))
-            count = np.where(reset, 0, count)
-            qn = qn & ~reset
-            ds = bump(_proj(v - alpha * g, lb, ub) - v)
-            d = np.where(qn, dq, ds)
-            d = np.where(active, d, 0.0)
-            lam = np.ones(B)
-            vt = trial(lam, d, active, v, ~qn)             # a finished instance's trial point is its v
-            gts = _dot(g, vt - v)
-            if not active.any():
-                break
-            started = active.copy()
-            nbt = np.zeros(B, dtype=np.int64)
-            lhs, rhs_at, Jt0 = np.full(B, np.nan), np.full(B, np.nan), None
-            for ls in range(maxBacktracks):
-                Jt, gt = evaluate(vt)
-                Jt, gt = np.array(Jt, dtype=np.float64), np.array(gt, dtype=np.float64)
-                Jt0 = Jt.copy() if ls == 0 else Jt0
-                # k_lbfgs_accept
-                pending = accepted == 0
-                rhs = J + 1e-4 * gts
-                decide_sign("g'(vt - v) < 0", pending, gts, _dot(np.abs(g), np.abs(vt - v)))
-                decide("Armijo", pending & (gts < 0.0), Jt, rhs)
-                ok = pending & (gts < 0.0) & (Jt <= rhs)    # a NaN Jt is a rejection
-                accepted[ok] = 2
-                lhs[ok], rhs_at[ok] = Jt[ok], rhs[ok]
-                rej = pending & ~ok
-                lam = np.where(rej, 0.5 * lam, lam)
-                vt = trial(lam, d, rej, vt, np.zeros(B, dtype=bool))
-                gts = np.where(rej, _dot(g, vt - v), gts)
-                nbt += rej
-                if not rej.any():
-                    break
-            # k_lbfgs_update
-            iters += active
-            take = active & (accepted == 2)
-            s, y = vt - v, gt - g
-            sty, sts, yty = _dot(s, y), _dot(s, s), _dot(y, y)
-            smax = np.fmax.reduce(np.abs(s), axis=0, initial=0.0)
-            v = np.where(take, vt, v)
-            g = np.where(take, gt, g)
-            J = np.where(take, Jt, J)
-            decide("s'y > 0", take, sty, 0.0)
-            decide_sign("s'y > 0", take, sty, _dot(np.abs(s), np.abs(y)))
-            an = np.where(sty > 0.0, sts / np.fmax(sty, 1e-300), 1e3)
-            alpha = np.where(take, bump(np.fmin(np.fmax(an, 1e-10), 1e10)), alpha)
-            decide("pair stored", take, sty, EPS_PAIR * yty)
-            store = take & (sty > EPS_PAIR * yty)
-            at = (head[None, None, :] == np.arange(pairs)[:, None, None]) & store[None, None, :]
-            S = np.where(at, s[None], S)
-            Y = np.where(at, y[None], Y)
-            rho = np.where(at[:, 0, :], (1.0 / sty)[None], rho)
-            head = np.where(store, (head + 1) % pairs, head)
-            count = np.where(store, np.minimum(count + 1, pairs), count)
-            decide("step <= TolX", take, smax, TolX)
-            tolx = take & (smax <= TolX)
-            failed = started & ~take
-            count = np.where(failed & qn, 0, count)     # a failed search on a quasi-Newton direction: drop the pairs, go on
-            active = (take & ~tolx) | (failed & qn)     # on SPG's direction the instance stops where it is
-            steps.append(SimpleNamespace(started=started, accepted=take, failed=failed, tolx=tolx, backtracks=nbt, Jt=lhs,
-                                         rhs=rhs_at, lam=lam.copy(), Jt0=Jt0, qn=qn.copy(), reset=reset, stored=store,
-                                         skipped=take & ~store, sty=sty, count=count.copy()))
-            snapshot()
-        while len(snap) < MaxIter + 1:
-            snapshot()
-    last = snap[-1]
-    return SimpleNamespace(v=last.v, J=last.J, iterations=last.iterations, converged=last.converged, pgn=last.pgn,
-                           backtracks=np.array([s.backtracks for s in steps]).reshape(len(steps), B),
-                           margin=last.margin, margins=margins, active=last.active, snap=snap, steps=steps)
+    (v, J, iterations, converged, pgn, backtracks, margin, active, snap, steps) and margins (margin per kind of decision); a
+    step record has in addition qn (the direction was a quasi-Newton one), reset (the safeguard dropped the pairs), stored /
+    skipped (the pair of an accepted step was stored / failed its test), sty, count (pairs held after the iteration)."""
+    r, st = run_twin(evaluate, v0, Lb, Ub, TolX, TolFun, MaxIter, maxBacktracks, ulp_seed,
+                     (_lbfgs_start, _lbfgs_direction, _lbfgs_accept, _lbfgs_update), pairs=pairs)
+    r.margins = st.margins
+    return r
 
 
 def counted(evaluate):
@@ -255,7 +180,6 @@ PURPOSE_CPU = ("blocks257", dict(batch=16, nB=41, N=200, T=40.0, K=500, pairs=8,
 
 
 def make_case(name):
-    from tests.spg_twin import make_inputs
     base, over = name if isinstance(name, tuple) else LCASES[name]
     over = dict(over)
     pairs = over.pop("pairs")
@@ -266,7 +190,6 @@ def make_case(name):
 
 def check_case_purpose(c, tw, dec, Lb, Ub):
     """what the case was made for occurs among the decisive instances `dec` of the twin run `tw`"""
-    from tests.spg_twin import INDECISIVE_CAP
     name, B = c.name, c.batch
     assert np.count_nonzero(~dec) <= INDECISIVE_CAP * B, (name, "indecisive", int(np.count_nonzero(~dec)), B)
     moved = np.any([st.accepted for st in tw.steps], axis=0)

@@ -1,10 +1,13 @@
 """The iteration of the batched shooting driver in plain NumPy (a helper module, not a test file).
 
-`spg_twin` restates ocs_single_shooting_batch_dev (csrc/ocs_shooting.cpp:98-115) and the five k_spg_* kernels
+`spg_twin` restates ocs_single_shooting_batch_dev (csrc/ocs_shooting.cpp) and the five k_spg_* kernels
 (csrc/ocs_shooting_kernels.hip) statement by statement, every instance a column of [rows][B] arrays, no Python loop
 over instances.  The objective and its gradient come from a callback, so the same twin runs on the CPU oracle
 (tests/test_spg_twin.py) and on the library's own nlp_objective_dev (tests/test_gpu_shooting_driver.py), where it
 then sees the very bits the driver sees and only the bookkeeping is under test.
+
+The driver's loop is `run_twin`, once for both algorithms (the other is tests/lbfgs_twin.py): an algorithm is its phases
+direction / accept / update, plain functions on the state `st` of a run.  The kernels' shared helpers are restated once.
 
 `CASES` / `make_inputs` is the one table of cases and seeds both files use; `check_purpose` asserts on a twin run
 what makes a case non-vacuous."""
@@ -17,11 +20,11 @@ DECISIVE_MARGIN = 1e-9      # three orders above the 1e-12 parity of the evaluat
 INDECISIVE_CAP = 0.05       # of the batch
 
 
-def _proj(w, lb, ub):                                   # spg_proj, kernels.hip:12
+def _proj(w, lb, ub):                                   # proj
     return np.fmin(np.fmax(w, lb[:, None]), ub[:, None])
 
 
-def _pgn(v, g, lb, ub):                                 # kernels.hip:19-23, :37-41, :119-123
+def _pgn(v, g, lb, ub):                                 # pg_norm
     return np.fmax.reduce(np.abs(_proj(v - g, lb, ub) - v), axis=0, initial=0.0)
 
 
@@ -31,11 +34,149 @@ def _rel(a, b):
     return np.where(np.isnan(r), np.inf, r)             # a NaN side decides the comparison whatever the other is
 
 
-def _dot(a, b):                                         # the kernels' running sums, row after row (:52-58, :94-99)
+def _dot(a, b, fr=None):                                # the kernels' running sums, row after row (over the rows `fr`)
     s = np.zeros(a.shape[1])
     for i in range(a.shape[0]):
-        s = s + a[i] * b[i]
+        s = s + (a[i] * b[i] if fr is None else np.where(fr[i], a[i] * b[i], 0.0))
     return s
+
+
+def note(st, what, mask, r):                            # the instances of `mask` decided something at relative distance r
+    st.margin[mask] = np.minimum(st.margin, r)[mask]
+    m = st.margins.setdefault(what, np.full(st.margin.shape, np.inf))   # the same per kind of decision (for the reader
+    m[mask] = np.minimum(m, r)[mask]                                    # of a failing case)
+
+
+def decide(st, what, mask, a, b):                       # the instances of `mask` take the comparison a ? b
+    note(st, what, mask, _rel(a, b))
+
+
+def decide_sign(st, what, mask, value, scale):          # the sign of `value`, measured on the scale of its terms
+    r = np.abs(value) / np.fmax(scale, 1e-300)          # (|x - 0| / max(|x|, 0) is 1 for every x != 0)
+    note(st, what, mask, np.where(np.isnan(r), np.inf, r))
+
+
+def goes_on(st):                                        # goes_on: the stopping test of both direction kernels
+    pgn = _pgn(st.v, st.g, st.lb, st.ub)
+    decide(st, "pgn <= TolFun", st.active, pgn, st.TolFun)
+    st.active = st.active & (pgn > st.TolFun)           # !(pgn > TolFun) stops, a NaN norm too
+    st.accepted = np.where(st.active, 0, 1)             # a finished instance's trial point is its v (the callers' where)
+
+
+def halve_step(st, rej):                                # halve_step
+    st.lam = np.where(rej, 0.5 * st.lam, st.lam)
+    st.vt = np.where(rej, _proj(st.v + st.lam * st.d, st.lb, st.ub), st.vt)
+
+
+def take_step(st, take):
+    """step_rows with `take` and step_taken: v, g, J move to the accepted point, Barzilai-Borwein step length of the next
+    iteration, stop on a small step.  Returns s, y, s'y and the instances stopped by TolX."""
+    s, y = st.vt - st.v, st.gt - st.g
+    sty, sts = _dot(s, y), _dot(s, s)
+    smax = np.fmax.reduce(np.abs(s), axis=0, initial=0.0)
+    st.v = np.where(take, st.vt, st.v)
+    st.g = np.where(take, st.gt, st.g)
+    st.J = np.where(take, st.Jt, st.J)
+    decide(st, "s'y > 0", take, sty, 0.0)
+    decide_sign(st, "s'y > 0", take, sty, _dot(np.abs(s), np.abs(y)))
+    an = np.where(sty > 0.0, sts / np.fmax(sty, 1e-300), 1e3)
+    st.alpha = np.where(take, st.bump(np.fmin(np.fmax(an, 1e-10), 1e10)), st.alpha)
+    decide(st, "step <= TolX", take, smax, st.TolX)
+    return s, y, sty, take & (smax <= st.TolX)
+
+
+def run_twin(evaluate, v0, Lb, Ub, TolX, TolFun, MaxIter, maxBacktracks, ulp_seed, phases, **own):
+    """ocs_single_shooting_batch_dev: the loop of both algorithms on the state `st` (`own`: the algorithm's options), phases
+    = (start, direction, accept, update).  start(st) adds the algorithm's state after k_spg_init; direction(st) is the
+    Direction phase; accept(st, pending) the Accept phase on the instances still waiting: it returns (accepted now, the
+    right-hand side of their test) and gives the others their next trial point; update(st, started) the Update phase: it
+    returns (step taken, stopped by TolX, the algorithm's entries of the step record).  Returns the result and `st`."""
+    start, direction, accept, update = phases
+    st = SimpleNamespace(v=np.array(v0, dtype=np.float64, copy=True), TolX=TolX, TolFun=TolFun, margins={}, **own)
+    nV, B = st.v.shape
+    st.lb = np.full(nV, -np.inf) if Lb is None else np.asarray(Lb, dtype=np.float64).ravel()
+    st.ub = np.full(nV, np.inf) if Ub is None else np.asarray(Ub, dtype=np.float64).ravel()
+    rng = None if ulp_seed is None else np.random.default_rng(ulp_seed)
+    one_ulp = lambda x: np.nextafter(x, np.where(rng.integers(0, 2, size=x.shape) == 1, np.inf, -np.inf))
+    st.bump = bump = (lambda x: x) if rng is None else one_ulp
+    st.margin, snap, steps = np.full(B, np.inf), [], []
+    arrays = lambda Jg: (np.array(Jg[0], dtype=np.float64), np.array(Jg[1], dtype=np.float64))
+
+    def snapshot():                                     # k_spg_finish
+        pgn = _pgn(st.v, st.g, st.lb, st.ub)
+        snap.append(SimpleNamespace(v=st.v.copy(), J=st.J.copy(), iterations=st.iters.copy(), active=st.active.copy(),
+                                    pgn=pgn, converged=pgn <= 10.0 * TolFun,
+                                    margin=np.minimum(st.margin, _rel(pgn, 10.0 * TolFun))))
+
+    with np.errstate(all="ignore"):
+        st.J, st.g = arrays(evaluate(st.v))
+        # k_spg_init
+        st.alpha = bump(1.0 / np.fmax(_pgn(st.v, st.g, st.lb, st.ub), 1e-12))
+        st.active = np.ones(B, dtype=bool)
+        st.iters = np.zeros(B, dtype=np.int64)
+        start(st)
+        snapshot()
+        for it in range(MaxIter):
+            st.it = it
+            direction(st)
+            if not st.active.any():                     # nactive == 0
+                break
+            started = st.active.copy()
+            nbt = np.zeros(B, dtype=np.int64)
+            lhs, rhs_at, Jt0 = np.full(B, np.nan), np.full(B, np.nan), None
+            for ls in range(maxBacktracks):
+                st.Jt, st.gt = arrays(evaluate(st.vt))
+                Jt0 = st.Jt.copy() if ls == 0 else Jt0
+                pending = st.accepted == 0              # the accept kernels return on accepted[b] != 0
+                ok, rhs = accept(st, pending)
+                st.accepted[ok] = 2
+                lhs[ok], rhs_at[ok] = st.Jt[ok], rhs[ok]
+                nbt += pending & ~ok
+                if not (pending & ~ok).any():           # nrejected == 0
+                    break
+            take, tolx, rec = update(st, started)
+            steps.append(SimpleNamespace(started=started, accepted=take, failed=started & ~take, tolx=tolx, backtracks=nbt,
+                                         Jt=lhs, rhs=rhs_at, lam=st.lam.copy(), Jt0=Jt0, **rec))
+            snapshot()
+        while len(snap) < MaxIter + 1:                  # the loop ended early: later calls return the same
+            snapshot()
+    backtracks = np.array([s.backtracks for s in steps]).reshape(len(steps), B)
+    return SimpleNamespace(**vars(snap[-1]), backtracks=backtracks, snap=snap, steps=steps), st   # v, J, ... of the last k
+
+
+def _spg_start(st):                                     # k_spg_init: the history
+    st.hist = np.tile(st.J, (st.memory, 1))
+    st.nonmonotone = np.zeros(st.J.shape, dtype=bool)
+
+
+def _spg_direction(st):                                 # k_spg_direction
+    goes_on(st)
+    d = st.bump(_proj(st.v - st.alpha * st.g, st.lb, st.ub) - st.v)    # spg_direction, SPG's form
+    st.d = np.where(st.active, d, 0.0)
+    st.vt = np.where(st.active, _proj(st.v + st.d, st.lb, st.ub), st.v)
+    st.gtd = _dot(st.g, st.d)
+    st.fmx = st.hist[0].copy()
+    for m in range(1, st.memory):
+        st.fmx = np.fmax(st.fmx, st.hist[m])
+    st.lam = np.ones(st.J.shape)
+
+
+def _spg_accept(st, pending):                           # k_spg_accept
+    rhs = st.fmx + 1e-4 * st.lam * st.gtd
+    decide(st, "Armijo", pending, st.Jt, rhs)
+    ok = pending & (st.Jt <= rhs)                       # a NaN Jt is a rejection
+    halve_step(st, pending & ~ok)
+    return ok, rhs
+
+
+def _spg_update(st, started):                           # k_spg_update
+    st.iters += st.active                               # a failed line search counts too
+    take = st.active & (st.accepted == 2)
+    st.nonmonotone |= take & (st.Jt > st.J)
+    tolx = take_step(st, take)[3]
+    st.active = take & ~tolx                            # a failed line search stops where it is
+    st.hist[st.it % st.memory] = st.J                   # every instance, every iteration
+    return take, tolx, {}
 
 
 def spg_twin(evaluate, v0, Lb, Ub, TolX, TolFun, MaxIter, memory, maxBacktracks, ulp_seed=None):
@@ -44,105 +185,10 @@ def spg_twin(evaluate, v0, Lb, Ub, TolX, TolFun, MaxIter, memory, maxBacktracks,
     GPU test).  Returns v, J, iterations, converged, pgn, and per instance: backtracks [iterations run][B], nonmonotone
     (an accepted step had Jt > J), margin (smallest relative distance over every comparison that decided something);
     `snap[k]` is the state a call with MaxIter = k returns (k = 0..MaxIter), `steps[it]` the record of iteration it."""
-    v = np.array(v0, dtype=np.float64, copy=True)
-    nV, B = v.shape
-    lb = np.full(nV, -np.inf) if Lb is None else np.asarray(Lb, dtype=np.float64).ravel()      # cpp:58-60
-    ub = np.full(nV, np.inf) if Ub is None else np.asarray(Ub, dtype=np.float64).ravel()
-    rng = None if ulp_seed is None else np.random.default_rng(ulp_seed)
-
-    def bump(x):
-        if rng is None:
-            return x
-        return np.nextafter(x, np.where(rng.integers(0, 2, size=x.shape) == 1, np.inf, -np.inf))
-
-    margin = np.full(B, np.inf)
-
-    def decide(mask, a, b):                             # the instances of `mask` take the comparison a ? b
-        margin[mask] = np.minimum(margin, _rel(a, b))[mask]
-
-    snap, steps = [], []
-
-    def snapshot():                                     # k_spg_finish, kernels.hip:115-126 (cpp:115)
-        pgn = _pgn(v, g, lb, ub)
-        snap.append(SimpleNamespace(v=v.copy(), J=J.copy(), iterations=iters.copy(), active=active.copy(), pgn=pgn,
-                                    converged=pgn <= 10.0 * TolFun,
-                                    margin=np.minimum(margin, _rel(pgn, 10.0 * TolFun))))
-
-    with np.errstate(all="ignore"):
-        J, g = evaluate(v)                              # cpp:98
-        J, g = np.array(J, dtype=np.float64), np.array(g, dtype=np.float64)
-        # k_spg_init, kernels.hip:15-28
-        alpha = bump(1.0 / np.fmax(_pgn(v, g, lb, ub), 1e-12))
-        hist = np.tile(J, (memory, 1))
-        active = np.ones(B, dtype=bool)
-        iters = np.zeros(B, dtype=np.int64)
-        nonmonotone = np.zeros(B, dtype=bool)
-        snapshot()
-        for it in range(MaxIter):                       # cpp:100
-            # k_spg_direction, kernels.hip:31-66
-            pgn = _pgn(v, g, lb, ub)
-            decide(active, pgn, TolFun)
-            active = active & (pgn > TolFun)            # :42  !(pgn > TolFun) stops, a NaN norm too
-            accepted = np.where(active, 0, 1)           # :46, :64
-            d = bump(_proj(v - alpha * g, lb, ub) - v)  # :54
-            d = np.where(active, d, 0.0)
-            vt = np.where(active, _proj(v + d, lb, ub), v)   # :47 a finished instance's trial point is its v; :56
-            gtd = _dot(g, d)                            # :57
-            fmx = hist[0].copy()                        # :59-60
-            for m in range(1, memory):
-                fmx = np.fmax(fmx, hist[m])
-            lam = np.ones(B)                            # :63
-            if not active.any():                        # cpp:103
-                break
-            started = active.copy()
-            nbt = np.zeros(B, dtype=np.int64)
-            lhs, rhs_at, Jt0 = np.full(B, np.nan), np.full(B, np.nan), None
-            for ls in range(maxBacktracks):             # cpp:104
-                Jt, gt = evaluate(vt)                   # cpp:105
-                Jt, gt = np.array(Jt, dtype=np.float64), np.array(gt, dtype=np.float64)
-                Jt0 = Jt.copy() if ls == 0 else Jt0
-                # k_spg_accept, kernels.hip:70-83
-                pending = accepted == 0                 # :72
-                rhs = fmx + 1e-4 * lam * gtd            # :75
-                decide(pending, Jt, rhs)
-                ok = pending & (Jt <= rhs)              # a NaN Jt is a rejection
-                accepted[ok] = 2                        # :76
-                lhs[ok], rhs_at[ok] = Jt[ok], rhs[ok]
-                rej = pending & ~ok
-                lam = np.where(rej, 0.5 * lam, lam)     # :79-80
-                vt = np.where(rej, _proj(v + lam * d, lb, ub), vt)     # :81
-                nbt += rej
-                if not rej.any():                       # cpp:108
-                    break
-            # k_spg_update, kernels.hip:86-112
-            iters += active                             # :91 (a failed line search counts too)
-            take = active & (accepted == 2)             # :92
-            s, y = vt - v, gt - g                       # :96
-            sty, sts = _dot(s, y), _dot(s, s)           # :97-98
-            smax = np.fmax.reduce(np.abs(s), axis=0, initial=0.0)   # :99
-            nonmonotone |= take & (Jt > J)
-            v = np.where(take, vt, v)                   # :100
-            g = np.where(take, gt, g)                   # :101
-            J = np.where(take, Jt, J)                   # :103
-            decide(take, sty, 0.0)
-            # |sty - 0| / max(|sty|, 0) is 1 for every sty != 0: measure the sign of sty on the scale of its terms as well
-            with_scale = np.abs(sty) / np.fmax(_dot(np.abs(s), np.abs(y)), 1e-300)
-            margin[take] = np.minimum(margin, np.where(np.isnan(with_scale), np.inf, with_scale))[take]
-            an = np.where(sty > 0.0, sts / np.fmax(sty, 1e-300), 1e3)       # :104
-            alpha = np.where(take, bump(np.fmin(np.fmax(an, 1e-10), 1e10)), alpha)   # :105
-            decide(take, smax, TolX)
-            tolx = take & (smax <= TolX)                # :106
-            active = take & ~tolx                       # :106, :108 a failed line search stops where it is
-            hist[it % memory] = J                       # :111 every instance, every iteration
-            steps.append(SimpleNamespace(started=started, accepted=take, failed=started & ~take, tolx=tolx,
-                                         backtracks=nbt, Jt=lhs, rhs=rhs_at, lam=lam.copy(), Jt0=Jt0))
-            snapshot()
-        while len(snap) < MaxIter + 1:                  # the loop ended early (cpp:103): later calls return the same
-            snapshot()
-    last = snap[-1]
-    return SimpleNamespace(v=last.v, J=last.J, iterations=last.iterations, converged=last.converged, pgn=last.pgn,
-                           backtracks=np.array([s.backtracks for s in steps]).reshape(len(steps), B),
-                           nonmonotone=nonmonotone, margin=last.margin, active=last.active, snap=snap, steps=steps)
+    r, st = run_twin(evaluate, v0, Lb, Ub, TolX, TolFun, MaxIter, maxBacktracks, ulp_seed,
+                     (_spg_start, _spg_direction, _spg_accept, _spg_update), memory=memory)
+    r.nonmonotone = st.nonmonotone
+    return r
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -154,6 +200,7 @@ _BLOCKS = dict(problem="testoc", basis="pwl", nB=7, N=40, T=4.0, start=(0.0, 1.0
 # the last `blowup` instances have m = 1.5 and start in [0, 0.5]: their first trial point P(v - g / pgn) drives the state
 # through zero, J is not finite there, and halving brings them back
 _BACK = dict(_BLOCKS, batch=130, T=20.0, start=(0.8, 1.0), memory=10, TolFun=1e-9, TolX=2e-3, seed=31, blowup=40)
+_CHEB = dict(_BLOCKS, problem="logistic", m=(3.0,), basis="cheb", nB=5, N=48, memory=10, K=6)
 CASES = {
     "blocks257": dict(_BLOCKS, batch=257, seed=11),
     "blocks600": dict(_BLOCKS, batch=600, seed=12),
@@ -164,14 +211,10 @@ CASES = {
     "zero": dict(_BLOCKS, batch=70, K=0, seed=51),
     "free": dict(_BLOCKS, problem="logistic", m=(3.0, 2.5), nB=6, batch=65, memory=10, start=(0.1, 0.5), free=(2,),
                  fsb=((0.45, 2.5),), crange=(0.2, 8.0), seed=61),
-    "cheb64on": dict(_BLOCKS, problem="logistic", m=(3.0,), basis="cheb", nB=5, N=48, batch=64, memory=10, K=6,
-                     fusion="on", seed=71),
-    "cheb64off": dict(_BLOCKS, problem="logistic", m=(3.0,), basis="cheb", nB=5, N=48, batch=64, memory=10, K=6,
-                      fusion="off", seed=71),
-    "cheb70on": dict(_BLOCKS, problem="logistic", m=(3.0,), basis="cheb", nB=5, N=48, batch=70, memory=10, K=6,
-                     fusion="on", seed=72),
-    "cheb70off": dict(_BLOCKS, problem="logistic", m=(3.0,), basis="cheb", nB=5, N=48, batch=70, memory=10, K=6,
-                      fusion="off", seed=72),
+    "cheb64on": dict(_CHEB, batch=64, fusion="on", seed=71),
+    "cheb64off": dict(_CHEB, batch=64, fusion="off", seed=71),
+    "cheb70on": dict(_CHEB, batch=70, fusion="on", seed=72),
+    "cheb70off": dict(_CHEB, batch=70, fusion="off", seed=72),
 }
 BOUNDS = [[0.0, 1.0]]
 
@@ -231,6 +274,39 @@ def oracle_setup(oracle, c):
             J[b], G[:, b], _ = oracle.nlp_objective(go, probs[b], co, c.x0[:, b], V[:, b], FreeInitStates=free)
         return J, G
     return evaluate, v0, Lb, Ub
+
+
+def device_setup(ocs, oracle, c):
+    """handles of a case on the GPU library `ocs`, v0, Lb, Ub, evaluate (its nlp_objective_dev on these handles, the whole
+    batch in one call) and solve(k, **options): what single_shooting_batch returns with MaxIter = k"""
+    import torch
+    tspan = oracle.linspace(0, c.T, c.N + 1)
+    integ = ocs.RK4Integrator(tspan)
+    if c.problem == "testoc":                           # parameter block [c m r]: c and m per trajectory
+        prob = ocs.TestOCProblem(P, BOUNDS)
+        prob.set_batch_params([0, 1], np.vstack([c.cs, c.ms]))
+    else:
+        prob = ocs.LogisticProblem(list(c.m), P["c"], P["r"], BOUNDS)
+        prob.set_batch_params([0], c.cs[None, :])
+    ctrl = (ocs.ChebyshevControl if c.basis == "cheb" else ocs.PWLinearControl)(integ.t, c.nB, 1)
+    if c.fusion:
+        ctrl.set_fusion(c.fusion)
+    v0, Lb, Ub = full_start(c, *((None, None) if c.basis == "cheb" else ctrl.compute_nlp_bounds(prob.ControlBounds)))
+
+    def evaluate(V, want_x0=False):
+        x0d = torch.tensor(c.x0, device="cuda:0").contiguous()
+        J, G = ocs.nlp_objective_dev(integ, prob, ctrl, x0d, torch.tensor(np.ascontiguousarray(V), device="cuda:0"),
+                                      FreeInitStates=list(c.free))
+        torch.cuda.synchronize()
+        return (J.cpu().numpy(), G.cpu().numpy()) + ((x0d.cpu().numpy(),) if want_x0 else ())
+
+    def solve(k, **kw):
+        r = ocs.single_shooting_batch(prob, c.x0, tspan, c.nB, Control=ctrl, Integrator=integ, v0=c.v0, MaxIter=k,
+                                      FreeInitStates=list(c.free), FreeStateBounds=c.fsb, constraints="ignore", **dict(c.opts, **kw))
+        torch.cuda.synchronize()
+        return SimpleNamespace(keys=sorted(r), pgn=r["projected_gradient"].cpu().numpy(),
+                               **{k: r[k].cpu().numpy() for k in ("v", "J", "iterations", "converged", "x0")})
+    return SimpleNamespace(c=c, v0=v0, Lb=Lb, Ub=Ub, evaluate=evaluate, solve=solve, integ=integ, prob=prob, ctrl=ctrl)
 
 
 def decisive_mask(tw, k=None):

@@ -15,8 +15,6 @@ Measured on an MI355X (spread of the two twin runs -> tolerance; largest driver-
   cheb70on 7.3e-11 -> 1.2e-9 (7.3e-12)    cheb70off 7.9e-11 -> 1.3e-9 (1.5e-11)
 (the Chebyshev cases have no bounds and steps of several hundred, backtrack has instances that recover from a non-finite
 trial point, free sits next to the collapse of its second state: there the iteration itself amplifies a last-place difference)."""
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 
@@ -40,42 +38,13 @@ def _case(ocs, oracle, name):
     """handles, the K + 1 driver runs and the two twin runs of a case (computed once, read-only)"""
     if name in _CACHE:
         return _CACHE[name]
-    import torch
-    dev = torch.device("cuda:0")
     c = T.make_inputs(name)
-    tspan = oracle.linspace(0, c.T, c.N + 1)
-    integ = ocs.RK4Integrator(tspan)
-    prob = (ocs.TestOCProblem(T.P, T.BOUNDS) if c.problem == "testoc"
-            else ocs.LogisticProblem(list(c.m), T.P["c"], T.P["r"], T.BOUNDS))
-    if c.problem == "testoc":                           # parameter block [c m r]: c and m per trajectory
-        prob.set_batch_params([0, 1], np.vstack([c.cs, c.ms]))
-    else:
-        prob.set_batch_params([0], c.cs[None, :])
-    ctrl = (ocs.ChebyshevControl if c.basis == "cheb" else ocs.PWLinearControl)(integ.t, c.nB, 1)
-    if c.fusion:
-        ctrl.set_fusion(c.fusion)
-    v0, Lb, Ub = T.full_start(c, *((None, None) if c.basis == "cheb" else ctrl.compute_nlp_bounds(prob.ControlBounds)))
-    free = list(c.free)
-
-    def evaluate(V, want_x0=False):
-        x0d = torch.tensor(c.x0, device=dev).contiguous()
-        J, G = ocs.nlp_objective_dev(integ, prob, ctrl, x0d, torch.tensor(np.ascontiguousarray(V), device=dev), FreeInitStates=free)
-        torch.cuda.synchronize()
-        return (J.cpu().numpy(), G.cpu().numpy()) + ((x0d.cpu().numpy(),) if want_x0 else ())
-
-    def solve(k):
-        r = ocs.single_shooting_batch(prob, c.x0, tspan, c.nB, Control=ctrl, Integrator=integ, v0=c.v0, MaxIter=k,
-                                      FreeInitStates=free, FreeStateBounds=c.fsb, constraints="ignore", **c.opts)
-        torch.cuda.synchronize()
-        return SimpleNamespace(v=r["v"].cpu().numpy(), J=r["J"].cpu().numpy(), iterations=r["iterations"].cpu().numpy(),
-                               converged=r["converged"].cpu().numpy(), pgn=r["projected_gradient"].cpu().numpy(),
-                               x0=r["x0"].cpu().numpy())
-
-    runs = [solve(k) for k in range(c.K + 1)]
-    tw = T.spg_twin(evaluate, v0, Lb, Ub, MaxIter=c.K, **c.opts)
-    tw2 = T.spg_twin(evaluate, v0, Lb, Ub, MaxIter=c.K, ulp_seed=c.seed, **c.opts)
-    _CACHE[name] = SimpleNamespace(c=c, runs=runs, tw=tw, tw2=tw2, v0=v0, Lb=Lb, Ub=Ub, evaluate=evaluate)
-    return _CACHE[name]
+    s = T.device_setup(ocs, oracle, c)
+    s.runs = [s.solve(k) for k in range(c.K + 1)]
+    s.tw = T.spg_twin(s.evaluate, s.v0, s.Lb, s.Ub, MaxIter=c.K, **c.opts)
+    s.tw2 = T.spg_twin(s.evaluate, s.v0, s.Lb, s.Ub, MaxIter=c.K, ulp_seed=c.seed, **c.opts)
+    _CACHE[name] = s
+    return s
 
 
 @pytest.mark.parametrize("name", list(T.CASES))

@@ -13,7 +13,6 @@ Measured on an MI355X (spread of the two twin runs -> tolerance; largest driver-
 (free257 sits next to the collapse of its second state and cheb257 has no bounds and steps of several hundred: there most pairs
 fail their test, the line searches run to 25 halvings, and the iteration itself amplifies a last-place difference.)"""
 import ctypes as C
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -35,46 +34,12 @@ def ocs():
 _CACHE = {}
 
 
-def _handles(ocs, oracle, c):
-    """handles of a case, evaluate (the library's nlp_objective_dev on them) and solve(k, **options)"""
-    import torch
-    dev = torch.device("cuda:0")
-    tspan = oracle.linspace(0, c.T, c.N + 1)
-    integ = ocs.RK4Integrator(tspan)
-    prob = (ocs.TestOCProblem(T.P, T.BOUNDS) if c.problem == "testoc"
-            else ocs.LogisticProblem(list(c.m), T.P["c"], T.P["r"], T.BOUNDS))
-    if c.problem == "testoc":                           # parameter block [c m r]: c and m per trajectory
-        prob.set_batch_params([0, 1], np.vstack([c.cs, c.ms]))
-    else:
-        prob.set_batch_params([0], c.cs[None, :])
-    ctrl = (ocs.ChebyshevControl if c.basis == "cheb" else ocs.PWLinearControl)(integ.t, c.nB, 1)
-    if c.fusion:
-        ctrl.set_fusion(c.fusion)
-    v0, Lb, Ub = T.full_start(c, *((None, None) if c.basis == "cheb" else ctrl.compute_nlp_bounds(prob.ControlBounds)))
-    free = list(c.free)
-
-    def evaluate(V, want_x0=False):
-        x0d = torch.tensor(c.x0, device=dev).contiguous()
-        J, G = ocs.nlp_objective_dev(integ, prob, ctrl, x0d, torch.tensor(np.ascontiguousarray(V), device=dev), FreeInitStates=free)
-        torch.cuda.synchronize()
-        return (J.cpu().numpy(), G.cpu().numpy()) + ((x0d.cpu().numpy(),) if want_x0 else ())
-
-    def solve(k, **kw):
-        r = ocs.single_shooting_batch(prob, c.x0, tspan, c.nB, Control=ctrl, Integrator=integ, v0=c.v0, MaxIter=k,
-                                      FreeInitStates=free, FreeStateBounds=c.fsb, constraints="ignore", **dict(c.opts, **kw))
-        torch.cuda.synchronize()
-        return SimpleNamespace(v=r["v"].cpu().numpy(), J=r["J"].cpu().numpy(), iterations=r["iterations"].cpu().numpy(),
-                               converged=r["converged"].cpu().numpy(), pgn=r["projected_gradient"].cpu().numpy(),
-                               x0=r["x0"].cpu().numpy(), keys=sorted(r))
-    return SimpleNamespace(c=c, v0=v0, Lb=Lb, Ub=Ub, evaluate=evaluate, solve=solve, integ=integ, prob=prob, ctrl=ctrl)
-
-
 def _case(ocs, oracle, name):
     """the K + 1 driver runs and the two twin runs of a case (computed once, read-only)"""
     if name in _CACHE:
         return _CACHE[name]
     c = L.make_case(name)
-    s = _handles(ocs, oracle, c)
+    s = T.device_setup(ocs, oracle, c)
     s.runs = [s.solve(k, Algorithm="lbfgs", pairs=c.pairs) for k in range(c.K + 1)]
     s.tw = L.lbfgs_twin(s.evaluate, s.v0, s.Lb, s.Ub, MaxIter=c.K, pairs=c.pairs, **c.opts)
     s.tw2 = L.lbfgs_twin(s.evaluate, s.v0, s.Lb, s.Ub, MaxIter=c.K, pairs=c.pairs, ulp_seed=c.seed, **c.opts)
@@ -174,7 +139,7 @@ def test_end_to_end_fewer_batch_evaluations(ocs, oracle):
     the twins fed by the GPU evaluations, the driver has no counter.
     Measured on an MI355X: SPG 66 evaluations (34 iterations at the most), L-BFGS 49 (20)."""
     c = L.make_case(L.PURPOSE_GPU)
-    s = _handles(ocs, oracle, c)
+    s = T.device_setup(ocs, oracle, c)
     es, el = L.counted(s.evaluate), L.counted(s.evaluate)
     sp = T.spg_twin(es, s.v0, s.Lb, s.Ub, MaxIter=c.K, **c.opts)
     lb = L.lbfgs_twin(el, s.v0, s.Lb, s.Ub, MaxIter=c.K, pairs=c.pairs, **c.opts)
