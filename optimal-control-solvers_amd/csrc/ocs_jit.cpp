@@ -267,11 +267,15 @@ int jit_build(const char* user_src, int nS, int nC, int npar, bool has_cc, bool 
   const char* hdr_src[] = {src_ocs_device_common_hpp, src_ocs_user_functor_hpp, src_ocs_rk4_kernels_hpp,
                            src_ocs_fbs_device_hpp, src_ocs_pipeline2_kernel_hpp, src_ocs_scan_kernel_hpp,
                            src_ocs_pipelinev_kernel_hpp, src_ocs_vscan_kernel_hpp, src_ocs_fold_kernel_hpp,
-                           src_ocs_costate_scan_kernel_hpp, src_ocs_costate_vscan_kernel_hpp};
+                           src_ocs_costate_scan_kernel_hpp, src_ocs_costate_vscan_kernel_hpp,
+                           src_ocs_pipeline2_body_inc, src_ocs_scan_body_inc};
   const char* hdr_name[] = {"ocs_device_common.hpp", "ocs_user_functor.hpp", "ocs_rk4_kernels.hpp",
                             "ocs_fbs_device.hpp", "ocs_pipeline2_kernel.hpp", "ocs_scan_kernel.hpp",
                             "ocs_pipelinev_kernel.hpp", "ocs_vscan_kernel.hpp", "ocs_fold_kernel.hpp",
-                            "ocs_costate_scan_kernel.hpp", "ocs_costate_vscan_kernel.hpp"};
+                            "ocs_costate_scan_kernel.hpp", "ocs_costate_vscan_kernel.hpp",
+                            "ocs_pipeline2_body.inc", "ocs_scan_body.inc"};   // (the two kernels' shared bodies)
+  constexpr int kNumHdr = sizeof(hdr_src) / sizeof(hdr_src[0]);
+  static_assert(kNumHdr == sizeof(hdr_name) / sizeof(hdr_name[0]), "one name per header");
   const std::vector<std::string> names = kernel_names(nS, nC, rowsep, fold);
   // Compiled code is kept for the life of the process, keyed by the full generated source (the kernel headers are fixed
   // per build of the library): creating the same problem again -- parameter studies, a test suite -- costs a module load
@@ -299,7 +303,7 @@ int jit_build(const char* user_src, int nS, int nC, int npar, bool has_cc, bool 
   int rtc_major = 0, rtc_minor = 0;
   if (r->Version) (void)r->Version(&rtc_major, &rtc_minor);
   const std::string disk = disk_cache_path(src + "\n// hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) +
-                                               " gfx950 -O3 -ffp-contract=fast", hdr_src, 11, names);
+                                               " gfx950 -O3 -ffp-contract=fast", hdr_src, kNumHdr, names);
   if (!cc && !disk.empty()) {
     auto loaded = std::make_shared<Compiled>();
     if (disk_cache_read(disk, *loaded, UK_COUNT)) {
@@ -309,7 +313,7 @@ int jit_build(const char* user_src, int nS, int nC, int npar, bool has_cc, bool 
   }
   if (!cc) {
     hiprtcProgram prog = nullptr;
-    if (r->CreateProgram(&prog, src.c_str(), "ocs_user_problem.hip", 11, hdr_src, hdr_name) != 0) {
+    if (r->CreateProgram(&prog, src.c_str(), "ocs_user_problem.hip", kNumHdr, hdr_src, hdr_name) != 0) {
       log = "hiprtcCreateProgram failed";
       return OCS_ERR_HIP;
     }
