@@ -116,6 +116,18 @@ int ocs_problem_dims(ocs_problem p, int *nS, int *nC);
  * accepted -- but no kernel of this problem reads such overrides, every pass then fails with OCS_ERR_UNSUPPORTED. */
 int ocs_problem_set_batch_params(ocs_problem p, int batch, const int *param_index, int nidx,
                                  const double *values);
+/* ControlBounds of its own per trajectory (batch extension; in the reference the bounds belong to the problem object,
+ * OCProblem.m:4, one pair per call).  lb, ub: nC x batch column-major, host; both NULL clears them, whatever `batch` is.
+ * OCS_ERR_INVALID: an entry with !(lb <= ub) (NaN included; -inf / +inf are allowed as in ocs_problem_create), one pointer
+ * NULL and the other not, batch < 1 with pointers given.  Calls on the problem must then use that batch (OCS_ERR_SHAPE
+ * otherwise); they may be set together with ocs_problem_set_batch_params, cost weights included, for the same batch.
+ * Read by: ocs_fb_sweep* (the default start u0 = each trajectory's lower bound, fb_sweep.m:23; every ControlChar clamp,
+ * make_from_symbolic.m:111, registry problems, plugins -- whose ocs_ControlChar receives the trajectory's lb, ub -- and
+ * OCS_PROBLEM_LQ).  The two-kernel sweep of ocs_fb_sweep_path 4 holds one bound per workgroup and is not taken while they are
+ * set: the sweep runs path 2 or 5.  ocs_problem_ControlChar, whose k free columns have no trajectory index, refuses the
+ * problem (OCS_ERR_UNSUPPORTED).  The integrator passes, ocs_compute_x_lam* and ocs_compute_equilibrium* (explicit lb, ub)
+ * read no control bounds; the shooting driver takes its bounds as arguments (ocs_single_shooting_batch_bounds_dev). */
+int ocs_problem_set_batch_bounds(ocs_problem p, int batch, const double *lb, const double *ub);
 /* value = F / dFdx_times_vec / dFdu_times_vec (OCProblem.m:12,16,19; TestOCProblem.m:22-38)
  * evaluated on the device for k columns; host pointers, shapes as in MATLAB. */
 int ocs_problem_F(ocs_problem p, int k, const double *t, const double *y, const double *u, double *out);
@@ -311,6 +323,12 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
                                   int nFree, const int *FreeInitStates, const double *Lb, const double *Ub,
                                   const ocs_ss_options *opt, double *J, int *iterations, int *converged,
                                   double *pgnorm, void *stream);
+/* The same with bounds of its own per instance: Lb, Ub DEVICE arrays, (nV+nFree) x batch batch-minor, or NULL (unbounded);
+ * every projection of instance b is on [Lb(:,b), Ub(:,b)].  OCS_ERR_INVALID if Lb > Ub anywhere, as for the shared vectors. */
+int ocs_single_shooting_batch_bounds_dev(ocs_integrator g, ocs_problem p, ocs_control c, int batch, double *x0,
+                                         double *v, int nFree, const int *FreeInitStates, const double *Lb,
+                                         const double *Ub, const ocs_ss_options *opt, double *J, int *iterations,
+                                         int *converged, double *pgnorm, void *stream);
 
 /* For a dense basis with at most 32 functions (ChebyshevControl) on an RK4Integrator, nlpObjective can apply
  * the basis inside the RK4 kernels (u and dJdu are never materialised).  mode: 0 automatic (large batches),

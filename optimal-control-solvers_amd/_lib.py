@@ -51,6 +51,7 @@ _SIG = {
     "ocs_problem_destroy": (C.c_int, [vp]),
     "ocs_problem_dims": (C.c_int, [vp, ip, ip]),
     "ocs_problem_set_batch_params": (C.c_int, [vp, C.c_int, ip, C.c_int, dp]),
+    "ocs_problem_set_batch_bounds": (C.c_int, [vp, C.c_int, dp, dp]),
     "ocs_problem_F": (C.c_int, [vp, C.c_int, dp, dp, dp, dp]),
     "ocs_problem_dFdx_times_vec": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp]),
     "ocs_problem_dFdu_times_vec": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp]),
@@ -95,6 +96,7 @@ _SIG = {
     "ocs_fbs_default_options": (C.c_int, [vp]),
     "ocs_ss_default_options": (C.c_int, [vp]),
     "ocs_single_shooting_batch_dev": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, ip, dp, dp, vp, vp, vp, vp, vp, vp]),
+    "ocs_single_shooting_batch_bounds_dev": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, ip, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ocs_compute_x_lam": (C.c_int, [vp, vp, C.c_int, dp, dp, dp, dp, dp]),
     "ocs_compute_x_lam_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ocs_fb_sweep": (C.c_int, [vp, vp, C.c_int, dp, vp, dp, dp, dp, dp, dp, dp, ip, dp]),

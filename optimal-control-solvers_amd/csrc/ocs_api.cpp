@@ -155,6 +155,29 @@ int ocs_problem_set_batch_params(ocs_problem p, int batch, const int* param_inde
   return OCS_OK;
 }
 
+int ocs_problem_set_batch_bounds(ocs_problem p, int batch, const double* lb, const double* ub) {
+  if (!p) return fail(OCS_ERR_INVALID, "null problem");
+  if (!lb && !ub) {  // clear
+    p->bb_batch = 0;
+    p->bb.clear();
+    p->version = next_version();
+    return OCS_OK;
+  }
+  if (!lb || !ub) return fail(OCS_ERR_INVALID, "give both lb and ub, or neither to clear");
+  if (batch < 1) return fail(OCS_ERR_INVALID, "batch must be >= 1");
+  const int nC = p->nC;
+  std::vector<double> m(2 * (size_t)nC * batch);   // nC x batch column-major -> [nC][batch]
+  double* um = m.data() + (size_t)nC * batch;
+  for (int b = 0; b < batch; ++b)
+    for (int c = 0; c < nC; ++c) {
+      const double lo = lb[(size_t)b * nC + c], hi = ub[(size_t)b * nC + c];
+      if (!(lo <= hi)) return fail(OCS_ERR_INVALID, "lb > ub (or NaN) at control %d of trajectory %d", c, b);
+      m[(size_t)c * batch + b] = lo;
+      um[(size_t)c * batch + b] = hi;
+    }
+  return set_batch_bounds_minor(p, batch, m.data(), um);
+}
+
 static int eval_common(ocs_problem p, int which, int k, const double* t, const double* y, const double* u,
                        const double* v, double* out) {
   if (!p || !t || !y || !u || !out || (which != 0 && !v) || k < 1) return fail(OCS_ERR_INVALID, "bad argument");

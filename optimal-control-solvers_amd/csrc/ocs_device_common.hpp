@@ -76,6 +76,12 @@ struct ParamSrc {
   }
 };
 
+// Bound c of trajectory b: from the shared vector [nC] (bstride 0: the plain load of before) or from the per-trajectory array
+// [nC][bstride] with bstride = batch (ProblemDesc::bb)
+__device__ static inline double bound_at(const double* v, int c, int bstride, int b) {
+  return bstride ? v[(size_t)c * bstride + b] : v[c];
+}
+
 // ---------------------------------------------------------------------------------------
 // per-step record table
 // ---------------------------------------------------------------------------------------

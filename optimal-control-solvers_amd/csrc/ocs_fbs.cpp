@@ -339,6 +339,17 @@ static int sweep_problem(ocs_problem_s* p, ocs_problem_s** out) {
                                                   p->bounds.data(), 1);
     if (rc != OCS_OK) return rc;
     p->shadow = q;
+    p->shadow_version = 0;
+  }
+  // ... but per-trajectory control bounds (ocs_problem_set_batch_bounds) do change: the twin, whose control update reads them,
+  // takes the same ones whenever the problem's version has moved since it last did (its own version then bumps with them)
+  if (p->shadow_version != p->version) {
+    if (p->bb_batch) {
+      const size_t half = (size_t)p->nC * p->bb_batch;
+      OCS_TRY(set_batch_bounds_minor(p->shadow, p->bb_batch, p->bb.data(), p->bb.data() + half));
+    } else if (p->shadow->bb_batch) {
+      OCS_TRY(ocs_problem_set_batch_bounds(p->shadow, 0, nullptr, nullptr));
+    }
     p->shadow_version = p->version;
   }
   *out = p->shadow;
@@ -398,6 +409,7 @@ int ocs_problem_ControlChar(ocs_problem p, int k, const double* t, const double*
   if (p->functor == Functor::User && !(p->user && p->user->has_cc))
     return fail(OCS_ERR_UNSUPPORTED, "the problem's source defines no ocs_ControlChar");
   if (p->pmask) return fail(OCS_ERR_UNSUPPORTED, "ControlChar: per-trajectory parameters have no meaning for k free columns");
+  if (p->bb_batch) return fail(OCS_ERR_UNSUPPORTED, "ControlChar: per-trajectory control bounds have no meaning for k free columns");
   OCS_TRY(upload_problem(p));
   const int nS = p->nS, nC = p->nC;
   DevBuf dt, dx, dl, dout;
@@ -566,16 +578,18 @@ int ocs_fb_sweep_dev(ocs_integrator g, ocs_problem p, int batch, const double* x
   // (registry problems: where the wave-specialised costate kernels and the gated state pass apply; hipRTC problems: row
   //  functions whose ocs_ControlChar reads the costate alone, fold_supported)
   const bool userfold = p->user != nullptr && fold_supported(pd, gd, batch);
-  const bool fold = !lqmc && fusedup && om == 1.0 && opt->fused_update_off == 0 &&
+  // (not with control bounds per trajectory: the fold kernels hold one scalar bound per workgroup)
+  const bool fold = !lqmc && !pd.bstride && fusedup && om == 1.0 && opt->fused_update_off == 0 &&
                     (userfold || (costate_forms_midpoints(pd, N, batch) && forward_gate_supported(pd, gd, batch) &&
                                   fold_supported(pd, gd, batch)));
   if (u0grid) {  // u = u0  :76
     HIP_TRY(hipMemcpyAsync(f->ugrid.p, u0grid, sizeof(double) * ugridN, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(f->uerr.p, u0err, sizeof(double) * uerrN, hipMemcpyDeviceToDevice, s));
   } else if (!fold) {  // u0 = ControlBounds(:,1)*ones(1,length(t))  :23
-    LAUNCH_TRY(launch_fill_rows(nT, nC, batch, p->d_lb.d(), f->ugrid.d(), s));
+    // (ControlBounds per trajectory: each instance's own lower bound)
+    LAUNCH_TRY(launch_fill_rows(nT, nC, batch, pd.lb, f->ugrid.d(), s, pd.bstride != 0));
     // (with the change measured on the grid nodes the separate error-point samples are never read)
-    if (!fusedup) LAUNCH_TRY(launch_fill_rows(nE, nC, batch, p->d_lb.d(), f->uerr.d(), s));
+    if (!fusedup) LAUNCH_TRY(launch_fill_rows(nE, nC, batch, pd.lb, f->uerr.d(), s, pd.bstride != 0));
   }
   const int* usel = (const int*)f->usel.p;  // selects the old / new buffer of the ERROR-POINT samples only
   // ---- the kernels of one sweep (all but the folded sweep of path 4) ---------------------------------------------------

@@ -421,6 +421,7 @@ struct ControlGridArgs {
   unsigned pmask;
   const double* lb;
   const double* ub;
+  int bstride;         // 0: lb / ub are [NC], shared; batch: [NC][batch], the instance's own (bound_at)
   const double* x;     // [N+1][ldx][B]
   int ldx;
   const double* xmid;  // [N][nS][B]
@@ -570,8 +571,8 @@ __global__ __launch_bounds__(256) void k_control_grid(const ControlGridArgs a) {
   double lb[NC], ub[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    lb[c] = a.lb[c];
-    ub[c] = a.ub[c];
+    lb[c] = bound_at(a.lb, c, a.bstride, b);
+    ub[c] = bound_at(a.ub, c, a.bstride, b);
   }
   const bool ownx = a.xmid == nullptr;  // no midpoint array of x: form those here as well
   if constexpr (NS > 4) {
@@ -742,6 +743,7 @@ struct ControlPtsArgs {
   unsigned pmask;
   const double* lb;
   const double* ub;
+  int bstride;         // 0: lb / ub are [NC], shared; batch: [NC][batch], the instance's own (bound_at)
   const double* x;
   int ldx;
   const double* lam;
@@ -840,8 +842,8 @@ __global__ __launch_bounds__(256) void k_control_pts(const ControlPtsArgs a) {
   for (int k = 0; k < NTU; ++k) tu[k] = as_uniform(a.TUQ)[(size_t)q * NTU + k];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    lb[c] = a.lb[c];
-    ub[c] = a.ub[c];
+    lb[c] = bound_at(a.lb, c, a.bstride, b);
+    ub[c] = bound_at(a.ub, c, a.bstride, b);
   }
   P::control_char(tu, x, lam, p, lb, ub, u);
   // Error-point mode: `out` holds the instance's current control at these points and is replaced in place.
@@ -890,8 +892,8 @@ __global__ __launch_bounds__(256) void k_control_pts_sorted(const ControlPtsArgs
     double lb[NC], ub[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      lb[c] = a.lb[c];
-      ub[c] = a.ub[c];
+      lb[c] = bound_at(a.lb, c, a.bstride, b);
+      ub[c] = bound_at(a.ub, c, a.bstride, b);
     }
     PchipSlide sl[NS], sx[NS];
 #pragma unroll

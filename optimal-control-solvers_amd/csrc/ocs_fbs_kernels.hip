@@ -85,7 +85,7 @@ int control_grid_parts(int N) { return (N + kPchipRun - 1) / kPchipRun; }
 int launch_control_grid(const ProblemDesc& p, const GridDesc& g, const FbsTables& t, int batch, const double* x, int ldx,
                         const double* xmid, const double* lam, double* u, const int* status, double* metric,
                         double relTol, double absTol, hipStream_t s, const int* gate, double relax) {
-  const ControlGridArgs a{g.N, batch, g.TU, p.ps, p.pb, p.pmask, p.lb, p.ub, x, ldx, xmid, lam, make_tab(t), t.TM, u,
+  const ControlGridArgs a{g.N, batch, g.TU, p.ps, p.pb, p.pmask, p.lb, p.ub, p.bstride, x, ldx, xmid, lam, make_tab(t), t.TM, u,
                           status, metric, relTol, absTol, gate, relax};
   if (p.functor == Functor::User) {
     void* args[] = {(void*)&a};
@@ -105,7 +105,7 @@ int launch_control_pts(const ProblemDesc& p, const FbsTables& t, int nq, const i
                        const double* TUQ, int batch, const double* x, int ldx, const double* lam, double* out,
                        const int* usel, long long odelta, double* metric, int* anyvalid, double relTol,
                        double absTol, hipStream_t s, double relax, const int* gate) {
-  ControlPtsArgs a{nq, batch, make_tab(t), KQ, SQ, TUQ, p.ps, p.pb, p.pmask, p.lb, p.ub, x, ldx, lam, out,
+  ControlPtsArgs a{nq, batch, make_tab(t), KQ, SQ, TUQ, p.ps, p.pb, p.pmask, p.lb, p.ub, p.bstride, x, ldx, lam, out,
                    usel, odelta, metric, anyvalid, relTol, absTol, relax};
   a.gate = gate;
   if (p.functor == Functor::User) {
@@ -177,7 +177,7 @@ int launch_control_pts_sorted(const ProblemDesc& p, const FbsTables& t, int nq, 
                               const double* TUQ, int batch, const double* x, int ldx, const double* lam, double* out,
                               double* metric, double relTol, double absTol, hipStream_t s, double relax, const int* gate) {
   if (!control_pts_sorted_ok(p)) return -1;
-  ControlPtsArgs a{nq, batch, make_tab(t), nullptr, SQ, TUQ, p.ps, p.pb, p.pmask, p.lb, p.ub, x, ldx, lam, out,
+  ControlPtsArgs a{nq, batch, make_tab(t), nullptr, SQ, TUQ, p.ps, p.pb, p.pmask, p.lb, p.ub, p.bstride, x, ldx, lam, out,
                    nullptr, 0, metric, nullptr, relTol, absTol, relax};
   a.gate = gate;
   if (p.functor == Functor::User) {

@@ -181,6 +181,12 @@ struct ocs_problem_s {
   // OCS_PROBLEM_LQ only: per-trajectory cost weights [nS + nC][pb_batch] (ProblemDesc::W); never together with pmask
   DevBuf d_w;
   bool has_w = false;
+  // control bounds of its own per trajectory (ocs_problem_set_batch_bounds): device [2 nC][bb_batch], batch-minor, rows
+  // 0 .. nC-1 the lower bounds, then the upper ones; bb_batch == 0: not set, the shared d_lb / d_ub are read.  `bb`: the same
+  // values on the host (the LQ problem hands them to its shadow, ocs_fbs.cpp sweep_problem)
+  DevBuf d_bb;
+  std::vector<double> bb;
+  int bb_batch = 0;
   unsigned long long version = 0;  // bumps whenever device-visible parameters change
   bool uploaded = false;
   // OCS_PROBLEM_LQ only: the same problem as generated device source (hipRTC), built on first use by the
@@ -277,6 +283,21 @@ inline int upload_problem(ocs_problem_s* p) {
   return OCS_OK;
 }
 
+// per-trajectory control bounds from host arrays that are batch-minor already: lbm, ubm [nC][batch] (validated by the caller)
+inline int set_batch_bounds_minor(ocs_problem_s* p, int batch, const double* lbm, const double* ubm) {
+  OCS_TRY(upload_problem(p));
+  const size_t half = (size_t)p->nC * batch;
+  std::vector<double> bb(2 * half);
+  memcpy(bb.data(), lbm, sizeof(double) * half);
+  memcpy(bb.data() + half, ubm, sizeof(double) * half);
+  OCS_TRY(p->d_bb.ensure(sizeof(double) * bb.size()));
+  HIP_TRY(hipMemcpy(p->d_bb.p, bb.data(), sizeof(double) * bb.size(), hipMemcpyHostToDevice));
+  p->bb.swap(bb);
+  p->bb_batch = batch;
+  p->version = next_version();
+  return OCS_OK;
+}
+
 inline ProblemDesc describe(const ocs_problem_s* p) {
   ProblemDesc d;
   d.functor = p->functor;
@@ -288,8 +309,10 @@ inline ProblemDesc describe(const ocs_problem_s* p) {
   d.pmask = p->pmask;
   d.W = p->has_w ? p->d_w.d() : nullptr;
   d.Wbatch = p->has_w ? p->pb_batch : 0;
-  d.lb = p->d_lb.d();
-  d.ub = p->d_ub.d();
+  d.bb = p->bb_batch ? p->d_bb.d() : nullptr;
+  d.bstride = p->bb_batch;
+  d.lb = d.bb ? d.bb : p->d_lb.d();
+  d.ub = d.bb ? d.bb + (size_t)p->nC * p->bb_batch : p->d_ub.d();
   d.user = p->user;
   d.version = p->version;
   return d;
@@ -343,6 +366,9 @@ inline int bind_problem(ocs_integrator_s* g, ocs_problem_s* p, int batch, hipStr
   if ((p->pmask || p->has_w) && p->pb_batch != batch)
     return fail(OCS_ERR_SHAPE, "problem has per-trajectory parameters for batch %d, call has batch %d",
                 p->pb_batch, batch);
+  if (p->bb_batch && p->bb_batch != batch)
+    return fail(OCS_ERR_SHAPE, "problem has per-trajectory control bounds for batch %d, call has batch %d",
+                p->bb_batch, batch);
   if (g->tc_prob != p || g->tc_version != p->version) {
     const int ntc = functor_ntc(p->functor, p->nS);
     const int ntu = functor_ntu(p->functor, p->nS);

@@ -29,8 +29,12 @@ struct ProblemDesc {
   // a mask word cannot name them; never set together with pmask.
   const double* W = nullptr;
   int Wbatch = 0;
-  const double* lb;   // device: control lower bounds [nC]
-  const double* ub;   // device: control upper bounds [nC]
+  const double* lb;   // device: control lower bounds [nC], or row 0 of bb
+  const double* ub;   // device: control upper bounds [nC], or row nC of bb
+  // per-trajectory control bounds [2 nC][bstride] (lower rows, then upper rows) or nullptr; bstride 0: lb / ub are the shared
+  // [nC] vectors, bstride = batch: bound c of trajectory b is lb[c * bstride + b] (bound_at, ocs_device_common.hpp)
+  const double* bb = nullptr;
+  int bstride = 0;
   const UserModule* user = nullptr;  // set for Functor::User
   unsigned long long version = 0;    // of the handle's device-visible parameters (cache key of tables derived from them)
 };
@@ -288,7 +292,8 @@ int launch_costate(const ProblemDesc& p, const GridDesc& g, int batch, const dou
 struct SpgArgs {
   int batch, nV, memory;
   double TolFun, TolX;
-  const double *lb, *ub;      // [nV]
+  const double *lb, *ub;      // [nV], or [nV][B] with bstride = B: bounds of its own per instance
+  int bstride;
   double *v, *g, *d, *vt, *gt;  // [nV][B]: iterate, its gradient, direction, trial point, its gradient
   double *J, *Jt, *alpha, *lam, *gtd, *fmax;  // [B]
   double* hist;               // [memory][B] last objective values (non-monotone line search)
@@ -316,6 +321,8 @@ struct ShootingArgs {
   int* converged;     // Finish: [B] or NULL, its verdict
 };
 int launch_shooting(SsPhase phase, const ShootingArgs& r, hipStream_t s);
+// bounds per instance: Lb, Ub [nV][B] or NULL (unbounded) -> lb, ub [nV][B]; *bad (device, zeroed by the caller) counts Lb > Ub
+int launch_ss_bounds(int nV, int batch, const double* Lb, const double* Ub, double* lb, double* ub, int* bad, hipStream_t s);
 int control_grid_parts(int N);
 // batched vectorInterpolant: V [n][nComp][B] -> out [nq][nComp][B]; method as OCS_INTERP_*; t: tables of the sample grid
 int launch_interp(int method, const FbsTables& t, int nComp, int nq, const int* KQ, const double* SQ, int batch,

@@ -33,6 +33,13 @@ static int carve(DevBuf& buf, size_t B, std::initializer_list<std::pair<T**, siz
   return OCS_OK;
 }
 
+// The solve of both entry points.  per_instance false: Lb, Ub are HOST vectors [nV + nFree] shared by the batch; true: DEVICE
+// arrays [nV + nFree][B], bounds of its own per instance.  Either may be NULL (unbounded).
+static int shooting_solve(const char* what, ocs_integrator g, ocs_problem p, ocs_control c, int batch, double* x0, double* v,
+                          int nFree, const int* FreeInitStates, const double* Lb, const double* Ub, bool per_instance,
+                          const ocs_ss_options* opt, double* J, int* iterations, int* converged, double* pgnorm,
+                          void* stream);
+
 extern "C" {
 
 int ocs_ss_default_options(ocs_ss_options* o) {
@@ -54,8 +61,27 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
                                   int nFree, const int* FreeInitStates, const double* Lb, const double* Ub,
                                   const ocs_ss_options* opt, double* J, int* iterations, int* converged,
                                   double* pgnorm, void* stream) {
+  return shooting_solve("ocs_single_shooting_batch_dev", g, p, c, batch, x0, v, nFree, FreeInitStates, Lb, Ub, false, opt, J,
+                        iterations, converged, pgnorm, stream);
+}
+
+// the same with bounds of its own per instance: Lb, Ub DEVICE arrays [nV+nFree][B], batch-minor, or NULL (unbounded)
+int ocs_single_shooting_batch_bounds_dev(ocs_integrator g, ocs_problem p, ocs_control c, int batch, double* x0, double* v,
+                                         int nFree, const int* FreeInitStates, const double* Lb, const double* Ub,
+                                         const ocs_ss_options* opt, double* J, int* iterations, int* converged,
+                                         double* pgnorm, void* stream) {
+  return shooting_solve("ocs_single_shooting_batch_bounds_dev", g, p, c, batch, x0, v, nFree, FreeInitStates, Lb, Ub, true, opt,
+                        J, iterations, converged, pgnorm, stream);
+}
+
+}  // extern "C"
+
+static int shooting_solve(const char* what, ocs_integrator g, ocs_problem p, ocs_control c, int batch, double* x0, double* v,
+                          int nFree, const int* FreeInitStates, const double* Lb, const double* Ub, bool per_instance,
+                          const ocs_ss_options* opt, double* J, int* iterations, int* converged, double* pgnorm,
+                          void* stream) {
   OCS_TRY(refuse_tiled(g, "ocs_single_shooting"));
-  OCS_TRACE("ocs_single_shooting_batch_dev");
+  OCS_TRACE(what);
   if (!g || !p || !c || !x0 || !v || !opt || !J || batch < 1 || nFree < 0) return fail(OCS_ERR_INVALID, "bad argument");
   if (opt->MaxIter < 0 || opt->memory < 1 || opt->maxBacktracks < 1 || !(opt->TolFun > 0))
     return fail(OCS_ERR_INVALID, "bad options");
@@ -74,10 +100,17 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
   OCS_TRY(vtbuf.ensure(vb));
   OCS_TRY(gtbuf.ensure(vb));
   OCS_TRY(hist.ensure(sizeof(double) * (size_t)opt->memory * B));
-  OCS_TRY(lbub.ensure(sizeof(double) * 2 * (size_t)nV));
+  OCS_TRY(lbub.ensure(sizeof(double) * 2 * (size_t)nV * (per_instance ? B : 1)));
   OCS_TRY(counter.ensure(sizeof(int)));
   OCS_TRY(conv.ensure(sizeof(int) * B));
-  {
+  if (per_instance) {   // the same refusal, counted on the device
+    int bad = 0;
+    HIP_TRY(hipMemsetAsync(counter.p, 0, sizeof(int), s));
+    LAUNCH_TRY(launch_ss_bounds(nV, batch, Lb, Ub, lbub.d(), lbub.d() + (size_t)nV * B, (int*)counter.p, s));
+    HIP_TRY(hipMemcpyAsync(&bad, counter.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad) return fail(OCS_ERR_INVALID, "Lb > Ub at %d coefficient(s) of the per-instance bounds", bad);
+  } else {
     std::vector<double> h(2 * (size_t)nV);
     const double inf = std::numeric_limits<double>::infinity();
     for (int i = 0; i < nV; ++i) {
@@ -100,7 +133,8 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
   a.TolFun = opt->TolFun;
   a.TolX = opt->TolX;
   a.lb = lbub.d();
-  a.ub = lbub.d() + nV;
+  a.ub = lbub.d() + (size_t)nV * (per_instance ? B : 1);
+  a.bstride = per_instance ? batch : 0;
   a.v = v;
   a.g = gbuf.d();
   a.d = dbuf.d();
@@ -156,5 +190,3 @@ int ocs_single_shooting_batch_dev(ocs_integrator g, ocs_problem p, ocs_control c
     if (!hc[b]) return OCS_NUM_NOT_CONVERGED;
   return OCS_OK;
 }
-
-}  // extern "C"

@@ -11,8 +11,10 @@ namespace ocs {
 
 // ---- the pieces both algorithms are made of, each over (args, instance b), every loop row after row
 
-// projection of coefficient i on its bounds
-__device__ static inline double proj(const SpgArgs& a, int i, double w) { return fmin(fmax(w, a.lb[i]), a.ub[i]); }
+// projection of coefficient i of instance b on its bounds (shared, or the instance's own: SpgArgs::bstride)
+__device__ static inline double proj(const SpgArgs& a, int i, int b, double w) {
+  return fmin(fmax(w, bound_at(a.lb, i, a.bstride, b)), bound_at(a.ub, i, a.bstride, b));
+}
 
 // ||P(v - g) - v||_inf
 __device__ static inline double pg_norm(const SpgArgs& a, int b) {
@@ -20,7 +22,7 @@ __device__ static inline double pg_norm(const SpgArgs& a, int b) {
   double pgn = 0.0;
   for (int i = 0; i < a.nV; ++i) {
     const double v = a.v[i * B + b], g = a.g[i * B + b];
-    pgn = fmax(pgn, fabs(proj(a, i, v - g) - v));
+    pgn = fmax(pgn, fabs(proj(a, i, b, v - g) - v));
   }
   return pgn;
 }
@@ -48,10 +50,10 @@ __device__ static inline double spg_direction(const SpgArgs& a, int b, bool on_b
   const double alpha = a.alpha[b];
   double gtd = 0.0;
   for (int i = 0; i < a.nV; ++i) {
-    const double v = a.v[i * B + b], g = a.g[i * B + b], w = proj(a, i, v - alpha * g);
+    const double v = a.v[i * B + b], g = a.g[i * B + b], w = proj(a, i, b, v - alpha * g);
     const double d = w - v;
     a.d[i * B + b] = d;
-    a.vt[i * B + b] = on_bound ? w : proj(a, i, v + d);
+    a.vt[i * B + b] = on_bound ? w : proj(a, i, b, v + d);
     gtd += g * d;
   }
   return gtd;
@@ -62,7 +64,7 @@ __device__ static inline void halve_step(const SpgArgs& a, int b) {
   const size_t B = (size_t)a.batch;
   const double half = 0.5 * a.lam[b];
   a.lam[b] = half;
-  for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = proj(a, i, a.v[i * B + b] + half * a.d[i * B + b]);
+  for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = proj(a, i, b, a.v[i * B + b] + half * a.d[i * B + b]);
 }
 
 // the accepted step: one pass over s = vt - v, y = gt - g with s'y, s's and max |s|; `row(i, s, y)` is what the algorithm
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_direction(LbfgsArgs l) {
     // q = g on the free coefficients (kept in d), 0 on the active set
     for (int i = 0; i < a.nV; ++i) {
       const double v = a.v[i * B + b], g = a.g[i * B + b];
-      const int fr = !((v == a.lb[i] && g > 0.0) || (v == a.ub[i] && g < 0.0));
+      const int fr = !((v == bound_at(a.lb, i, a.bstride, b) && g > 0.0) || (v == bound_at(a.ub, i, a.bstride, b) && g < 0.0));
       l.fr[i * B + b] = fr;
       a.d[i * B + b] = fr ? g : 0.0;
     }
@@ -224,7 +226,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_direction(LbfgsArgs l) {
       gtd += a.g[i * B + b] * d;
     }
     if (gtd < 0.0 && gtd >= -1.7976931348623157e308) {
-      for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = proj(a, i, a.v[i * B + b] + a.d[i * B + b]);
+      for (int i = 0; i < a.nV; ++i) a.vt[i * B + b] = proj(a, i, b, a.v[i * B + b] + a.d[i * B + b]);
     } else {  // not a finite descent direction: drop the pairs
       qn = 0;
       l.count[b] = 0;
@@ -283,6 +285,23 @@ __global__ __launch_bounds__(256) void k_lbfgs_update(LbfgsArgs l) {
     l.count[b] = min(l.count[b] + 1, l.pairs);
   }
   step_taken(a, b, r);
+}
+
+// Lb / Ub of a solve with bounds per instance: copies them into the driver's own arrays (a NULL side: unbounded) and counts the
+// entries with Lb > Ub (or NaN) into *bad, which refuses the solve
+__global__ __launch_bounds__(256) void k_ss_bounds(size_t n, const double* __restrict__ Lb, const double* __restrict__ Ub,
+                                                   double* __restrict__ lb, double* __restrict__ ub, int* __restrict__ bad) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double lo = Lb ? Lb[i] : -__builtin_inf(), hi = Ub ? Ub[i] : __builtin_inf();
+  lb[i] = lo;
+  ub[i] = hi;
+  if (!(lo <= hi)) atomicAdd(bad, 1);
+}
+int launch_ss_bounds(int nV, int batch, const double* Lb, const double* Ub, double* lb, double* ub, int* bad, hipStream_t s) {
+  const size_t n = (size_t)nV * batch;
+  k_ss_bounds<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(n, Lb, Ub, lb, ub, bad);
+  return hip_rc(hipGetLastError());
 }
 
 int launch_shooting(SsPhase phase, const ShootingArgs& r, hipStream_t s) {

@@ -27,6 +27,33 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(dp)
 
 
+def batch_bounds_host(lb, ub, ControlBounds):
+    """The arguments of OCProblem.set_batch_bounds as the pair (lb, ub) the library takes, each nC x batch column-major, or
+    None when both are None (clear).  A side given as None is the shared ControlBounds column repeated.  ValueError for a
+    wrong shape, different batches of lb and ub, or an entry with not (lb <= ub) (NaN included).  No device needed."""
+    if lb is None and ub is None:
+        return None
+    cb = np.asarray(ControlBounds, dtype=np.float64)
+    nC = cb.shape[0]
+    sides = {}
+    for name, val in (("lb", lb), ("ub", ub)):
+        if val is None:
+            continue
+        val = np.asarray(val, dtype=np.float64)
+        if val.ndim != 2 or val.shape[0] != nC or val.shape[1] < 1:
+            raise ValueError(f"{name} must be {nC} x batch, got shape {val.shape}")
+        sides[name] = val
+    if len(sides) == 2 and sides["lb"].shape[1] != sides["ub"].shape[1]:
+        raise ValueError(f"lb has batch {sides['lb'].shape[1]}, ub has batch {sides['ub'].shape[1]}")
+    batch = next(iter(sides.values())).shape[1]
+    lo = sides.get("lb", np.repeat(cb[:, 0:1], batch, axis=1))
+    hi = sides.get("ub", np.repeat(cb[:, 1:2], batch, axis=1))
+    if not np.all(lo <= hi):
+        c, b = np.argwhere(~(lo <= hi))[0]
+        raise ValueError(f"lb > ub (or NaN) at control {c} of trajectory {b}: {lo[c, b]} > {hi[c, b]}")
+    return np.array(lo, order="F", copy=True), np.array(hi, order="F", copy=True)
+
+
 class OCProblem:
     """OCProblem/OCProblem.m:1-24 -- abstract interface; concrete problems come from the registry."""
 
@@ -56,6 +83,22 @@ class OCProblem:
             raise ValueError("values must be len(index) x batch")
         check(lib.ocs_problem_set_batch_params(self._h, values.shape[1],
                                                index.ctypes.data_as(_lib.ip), index.size, _p(values)))
+
+    batch_bounds = None   # (lb, ub), each nC x batch, while set_batch_bounds is in force
+
+    def set_batch_bounds(self, lb=None, ub=None):
+        """ControlBounds of its own per trajectory (batch extension; OCProblem.m:4 has one pair per problem object): lb, ub
+        are nC x batch; one of them None keeps the shared ControlBounds on that side for every trajectory, both None clears.
+        fb_sweep_batch / fb_sweep_dev then start from and clamp to trajectory b's own bounds, single_shooting_batch clamps u0
+        and builds Lb / Ub per instance; ControlChar refuses the problem while they are set.  Calls must use that batch."""
+        pair = batch_bounds_host(lb, ub, self.ControlBounds)
+        if pair is None:
+            check(lib.ocs_problem_set_batch_bounds(self._h, 0, None, None))
+            self.batch_bounds = None
+            return self
+        check(lib.ocs_problem_set_batch_bounds(self._h, pair[0].shape[1], _p(pair[0]), _p(pair[1])))
+        self.batch_bounds = pair
+        return self
 
     def _cols(self, t):
         t = _f(np.atleast_1d(t)).ravel()

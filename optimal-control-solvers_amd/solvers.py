@@ -249,6 +249,27 @@ def initial_v_batch(control, u0, bounds, B):
     return np.stack([control.compute_initial_v(np.ascontiguousarray(u0c[:, b])) for b in range(B)], axis=1)
 
 
+def batch_bounds_start(control, u0, batch_bounds, B):
+    """Start and box of single_shooting_batch for a problem with ControlBounds per instance (OCProblem.set_batch_bounds;
+    batch_bounds = (lb, ub), each nC x B): what single_shooting.m would build for instance b's own problem, column by column --
+    u0 (shared or nC x B, as clamp_u0_batch) clamped to instance b's bounds (:56), v0(:, b) = compute_initial_v of it (:82),
+    [Lb(:, b), Ub(:, b)] = compute_nlp_bounds([lb(:, b), ub(:, b)]) (:89; unbounded for a control without that method).
+    Returns (v0, Lb, Ub), each nV x B.  No device needed."""
+    lo, hi = (np.asarray(a, dtype=np.float64) for a in batch_bounds)
+    nC = lo.shape[0]
+    if lo.shape != (nC, B) or hi.shape != (nC, B):
+        raise ValueError(f"the problem has control bounds for batch {lo.shape[1]}, the call has batch {B}")
+    a, per_instance = clamp_u0_batch(u0, np.tile([-np.inf, np.inf], (nC, 1)), B)    # (shape rules only: nothing to clamp to)
+    u0c = np.minimum(hi, np.maximum(lo, a if per_instance else a[:, None]))
+    v0 = np.stack([control.compute_initial_v(np.ascontiguousarray(u0c[:, b])) for b in range(B)], axis=1)
+    if hasattr(control, "compute_nlp_bounds"):
+        cols = [control.compute_nlp_bounds(np.column_stack([lo[:, b], hi[:, b]])) for b in range(B)]
+        Lb, Ub = np.stack([c[0] for c in cols], axis=1), np.stack([c[1] for c in cols], axis=1)
+    else:
+        Lb, Ub = np.full(v0.shape, -np.inf), np.full(v0.shape, np.inf)
+    return v0, Lb, Ub
+
+
 def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrator=None, u0=0.0, TolX=1e-5,
                           TolFun=3e-4, MaxIter=500, memory=10, FreeInitStates=(), FreeStateBounds=None, v0=None,
                           constraints="warn", maxBacktracks=None, Algorithm="spg", pairs=None):
@@ -273,6 +294,8 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     (nFree x 2, :91-94; default unbounded).
     u0: nC values shared by the instances, or nC x B, a start per instance (each instance's own uStar, as
     tests/solve_test_problem.m:37 passes 'u0', uStar'); clamped to the bounds and expanded with compute_initial_v.
+    A problem with ControlBounds per instance (OCProblem.set_batch_bounds): u0 is clamped to, and Lb / Ub are
+    compute_nlp_bounds of, instance b's own bounds (batch_bounds_start); FreeStateBounds stay shared.
     Returns a dict of device tensors: v [nV(+nFree)][B], J [B], iterations [B], converged [B],
     projected_gradient [B], x0 [nS][B] and `soln_of(b)` (J, v and the control callable of instance b)."""
     from ._lib import SS_ALGORITHMS, SsOptions
@@ -287,16 +310,20 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     B = x0.shape[1]
     x0d = torch.tensor(x0, device=dev).contiguous()
     nFree, fis = _fis(FreeInitStates)
+    per_instance = getattr(prob, "batch_bounds", None) is not None     # Lb, Ub are then nV x B
+    if per_instance:
+        v0b, Lb, Ub = batch_bounds_start(control, u0, prob.batch_bounds, B)
     if v0 is None:
-        v0 = initial_v_batch(control, u0, prob.ControlBounds, B)
+        v0 = v0b if per_instance else initial_v_batch(control, u0, prob.ControlBounds, B)
     else:
         v0 = np.asarray(v0, dtype=np.float64)
         v0 = np.repeat(v0[:, None], B, axis=1) if v0.ndim == 1 else v0
     nV = v0.shape[0]
-    if hasattr(control, "compute_nlp_bounds"):
-        Lb, Ub = control.compute_nlp_bounds(prob.ControlBounds)
-    else:
-        Lb, Ub = np.full(nV, -np.inf), np.full(nV, np.inf)
+    if not per_instance:
+        if hasattr(control, "compute_nlp_bounds"):
+            Lb, Ub = control.compute_nlp_bounds(prob.ControlBounds)
+        else:
+            Lb, Ub = np.full(nV, -np.inf), np.full(nV, np.inf)
     # The projected gradient iteration projects on a BOX: the constraint hooks of single_shooting.m:99-111
     # (compute_nonlcon, compute_lincon) have no counterpart here.  A control that defines them (ChebyshevControl's bounds
     # at the grid points) is iterated without them -- said once, not silently; single_shooting() honours them.
@@ -312,9 +339,16 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
         v0 = np.vstack([v0, x0[idx, :]])
         fsb = (np.tile([-np.inf, np.inf], (nFree, 1)) if FreeStateBounds is None
                else np.asarray(FreeStateBounds, dtype=np.float64).reshape(nFree, 2))
-        Lb = np.concatenate([Lb, fsb[:, 0]])                              # :91-94
-        Ub = np.concatenate([Ub, fsb[:, 1]])
-    Lb, Ub = _f(Lb).ravel().copy(), _f(Ub).ravel().copy()
+        if per_instance:
+            Lb = np.vstack([Lb, np.repeat(fsb[:, 0:1], B, axis=1)])       # :91-94
+            Ub = np.vstack([Ub, np.repeat(fsb[:, 1:2], B, axis=1)])
+        else:
+            Lb = np.concatenate([Lb, fsb[:, 0]])                          # :91-94
+            Ub = np.concatenate([Ub, fsb[:, 1]])
+    if per_instance:
+        Lb, Ub = (torch.tensor(np.ascontiguousarray(a), device=dev).contiguous() for a in (Lb, Ub))
+    else:
+        Lb, Ub = _f(Lb).ravel().copy(), _f(Ub).ravel().copy()
     v = torch.tensor(np.ascontiguousarray(v0), device=dev).contiguous()
     J = torch.empty(B, dtype=torch.float64, device=dev)
     pgn = torch.empty(B, dtype=torch.float64, device=dev)
@@ -328,9 +362,14 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
     o.algorithm = SS_ALGORITHMS[Algorithm.lower()]
     if pairs is not None:
         o.pairs = int(pairs)
-    rc = lib.ocs_single_shooting_batch_dev(integrator._h, prob._h, control._h, B, _dptr(x0d), _dptr(v), nFree, fis,
-                                           _p(Lb), _p(Ub), C.byref(o), _dptr(J), C.c_void_p(iters.data_ptr()), C.c_void_p(conv.data_ptr()), _dptr(pgn),
-                                           _stream())
+    if per_instance:
+        rc = lib.ocs_single_shooting_batch_bounds_dev(integrator._h, prob._h, control._h, B, _dptr(x0d), _dptr(v), nFree, fis,
+                                                      _dptr(Lb), _dptr(Ub), C.byref(o), _dptr(J), C.c_void_p(iters.data_ptr()),
+                                                      C.c_void_p(conv.data_ptr()), _dptr(pgn), _stream())
+    else:
+        rc = lib.ocs_single_shooting_batch_dev(integrator._h, prob._h, control._h, B, _dptr(x0d), _dptr(v), nFree, fis,
+                                               _p(Lb), _p(Ub), C.byref(o), _dptr(J), C.c_void_p(iters.data_ptr()), C.c_void_p(conv.data_ptr()), _dptr(pgn),
+                                               _stream())
     if rc < 0:
         check(rc)
     out = {"v": v, "J": J, "iterations": iters, "converged": conv.to(torch.bool), "projected_gradient": pgn, "x0": x0d,
