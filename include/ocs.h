@@ -40,7 +40,7 @@ extern "C" {
 #define OCS_ERR_HIP (-5)         /* a HIP call failed                             */
 #define OCS_ERR_UNSUPPORTED (-6) /* problem/shape not in the kernel registry       */
 #define OCS_NUM_NONFINITE 1      /* a returned J is NaN/Inf                        */
-#define OCS_NUM_NOT_CONVERGED 2  /* fb_sweep: at least one instance hit nSWEEPS    */
+#define OCS_NUM_NOT_CONVERGED 2  /* fb_sweep: at least one instance hit nSWEEPS; bvp_solver: at least one failed */
 
 /* ---- problem registry (device functors; see csrc/ocs_problems.hpp) ---- */
 #define OCS_PROBLEM_TEST 1     /* tests/TestOCProblem.m:22-38        params [c m r], nS=1, nC=1 */
@@ -401,6 +401,46 @@ int ocs_fb_sweep_path(ocs_integrator g);
  * states, no per-trajectory parameters); 0 otherwise, or if none has run.  It does not change ocs_fb_sweep_path: the
  * sweep loops are the same, only the two passes inside them differ. */
 int ocs_fb_sweep_matrix_core(ocs_integrator g);
+
+/* ---- soln = bvp_solver(prob, x0, tspan, options)   functions/bvp_solver.m:1-134 for a batch of instances ----
+ * The optimality system y' = optSys(t, y), y = [x; lam] (:105-109, through the same Gen-2 -> Gen-1 adapter as fb_sweep,
+ * ControlChar clamped to each trajectory's own bounds where they are set), with x(T0) = x0, lam(TF) = 0 (:66), is
+ * collocated with bvp4c's Simpson / Lobatto-IIIa formula on the N+1 nodes of `g` (an RK4Integrator; the mesh is fixed, h
+ * may vary) and solved per instance by a damped Newton iteration: Jacobian of optSys by forward differences, the linear
+ * system by block elimination over time (one pivoted solve per interval and per node), step lengths 1, 1/2, 1/4, ...
+ * accepted at ||Phi(y + a d)||_2 < (1 - 1e-4 a) ||Phi(y)||_2, stop at ||Phi||_inf <= NewtonTol.  An instance fails after
+ * MaxIter iterations, after maxBacktracks halvings without an accepted step, or on a singular pivot / non-finite value; it
+ * does not disturb the others.  bvp5c and its mesh adaptation are a MATLAB toolbox: results are those of the grid.
+ * Custom bcFunc / yLJac / yRJac / optJac (:74-84, :115) are not supported.
+ * Registry problems of the logistic family and plugin problems whose source defines ocs_ControlChar, nS <= 4, nC <= 2;
+ * OCS_PROBLEM_LQ and larger plugins: OCS_ERR_UNSUPPORTED.
+ * Fill the struct with ocs_bvp_default_options before setting fields: it may grow at its end. */
+typedef struct ocs_bvp_options {
+  double NewtonTol;   /* stop at ||Phi||_inf <= NewtonTol (default 1e-10) */
+  int MaxIter;        /* Newton iterations per instance (default 40) */
+  int maxBacktracks;  /* step halvings of one line search (default 12, at most 60) */
+  int nINTERP_PTS;    /* bvp_solver.m:20 */
+  int cost_row;       /* kept for the layout of ocs_fbs_options' callers: compute_x_lam_J (:132) integrates the augmented
+                         system, so the running-objective row of xaug is always written */
+} ocs_bvp_options;
+int ocs_bvp_default_options(ocs_bvp_options *o);
+/* device arrays, batch-minor: x0 [nS][B];
+ * the start (:87-98): y0 [N+1][2 nS][B] (a guess on the nodes), else u0grid [2N+1][nC][B] (the guess is x, lam of
+ * ocs_compute_x_lam_dev under that control), else both NULL: the constant [x0; 0] of bvpinit;
+ * out: ynodes [N+1][2 nS][B] the collocation solution; uInterp [nINTERP_PTS][nC][B] = ControlChar(interpPts, x(interpPts),
+ * lam(interpPts)) with pchip interpolants of ynodes (:124-126); xaug [N+1][nS+1][B], lam [N+1][nS][B], J [B]: compute_x_lam_J
+ * under the pchip of uInterp sampled on the 2N+1 grid (:132);
+ * iterations, converged (int) [B], resnorm [B] = ||Phi||_inf of ynodes.  The outputs of an instance that did not converge
+ * belong to its last iterate.  Returns OCS_NUM_NOT_CONVERGED if any instance failed.  One host round trip per iteration,
+ * a second one when some line search goes beyond its first three step lengths. */
+int ocs_bvp_solver_dev(ocs_integrator g, ocs_problem p, int batch, const double *x0, const ocs_bvp_options *opt,
+                       const double *y0, const double *u0grid, double *ynodes, double *xaug, double *lam,
+                       double *uInterp, double *J, int *iterations, int *converged, double *resnorm, void *stream);
+/* host: x0 nS x batch; y0 2nS x (N+1) x batch, u0grid nC x (2N+1) x batch or NULL; ynodes 2nS x (N+1) x batch; x, lam
+ * nS x (N+1) x batch; uInterp nC x nINTERP_PTS x batch; J, iterations, converged, resnorm batch */
+int ocs_bvp_solver(ocs_integrator g, ocs_problem p, int batch, const double *x0, const ocs_bvp_options *opt,
+                   const double *y0, const double *u0grid, double *ynodes, double *x, double *lam, double *uInterp,
+                   double *J, int *iterations, int *converged, double *resnorm);
 
 /* ---- the batch axis over the GPUs of one node (the reference has no batch axis and no parallelism:
  * every entry point integrates one trajectory, tests/solve_test_problem.m:37) ----

@@ -101,6 +101,9 @@ _SIG = {
     "ocs_compute_x_lam_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ocs_fb_sweep": (C.c_int, [vp, vp, C.c_int, dp, vp, dp, dp, dp, dp, dp, dp, ip, dp]),
     "ocs_fb_sweep_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ocs_bvp_default_options": (C.c_int, [vp]),
+    "ocs_bvp_solver": (C.c_int, [vp, vp, C.c_int, dp, vp, dp, dp, dp, dp, dp, dp, dp, ip, ip, dp]),
+    "ocs_bvp_solver_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ocs_multi_create": (C.c_int, [C.POINTER(vp), ip, C.c_int]),
     "ocs_multi_destroy": (C.c_int, [vp]),
     "ocs_multi_size": (C.c_int, [vp]),
@@ -146,6 +149,12 @@ class FbsOptions(C.Structure):
     _fields_ = [("uRelTol", C.c_double), ("uAbsTol", C.c_double), ("nSWEEPS", C.c_int),
                 ("nERROR_PTS", C.c_int), ("nINTERP_PTS", C.c_int), ("fused_update_off", C.c_int), ("nWINDOWS", C.c_int),
                 ("cost_row", C.c_int), ("uRelax", C.c_double)]
+
+
+class BvpOptions(C.Structure):
+    """struct ocs_bvp_options (include/ocs.h)."""
+    _fields_ = [("NewtonTol", C.c_double), ("MaxIter", C.c_int), ("maxBacktracks", C.c_int), ("nINTERP_PTS", C.c_int),
+                ("cost_row", C.c_int)]
 
 
 class SsOptions(C.Structure):

@@ -148,6 +148,12 @@ static int stage_out_states(DevBuf& stage, const double* xaug, double* x, int nS
   return OCS_OK;
 }
 
+namespace ocs {
+int fbs_ensure_tables(ocs_integrator_s* g) { return ensure_tables(g); }
+FbsTables fbs_tables(const ocs_integrator_s* g) { return tabs(g); }
+int fbs_build_points(ocs_integrator_s* g, int nq, DevBuf& K, DevBuf& S, DevBuf& T) { return build_points(g, nq, K, S, T); }
+}  // namespace ocs
+
 extern "C" {
 
 // vectorInterpolant(x, v, method)(tq) for a batch of sample sets on the device (functions/vectorInterpolant.m:1-12;

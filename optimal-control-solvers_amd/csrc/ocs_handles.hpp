@@ -202,9 +202,13 @@ struct ocs_problem_s {
 struct ocs_fbs_state;  // forward-backward-sweep workspace (ocs_fbs.cpp)
 void ocs_fbs_state_free(ocs_fbs_state* s);
 
+struct ocs_bvp_state;  // bvp_solver workspace (ocs_bvp.cpp)
+void ocs_bvp_state_free(ocs_bvp_state* s);
+
 struct ocs_integrator_s {
   using DevBuf = ocs::DevBuf;
   ocs_fbs_state* fbs = nullptr;
+  ocs_bvp_state* bvp = nullptr;
   ocs::LqWorkspace* lqws = nullptr;   // time-parallel LQ passes: chunk matrices of the bound problem + scratch
   int device = -1;   // HIP device current when the handle was created
   int rec_stride = 8;  // doubles per step record of the bound problem
@@ -250,6 +254,7 @@ struct ocs_integrator_s {
     if (tc_event) (void)hipEventDestroy(tc_event);
     delete leg2;
     if (fbs) ocs_fbs_state_free(fbs);
+    if (bvp) ocs_bvp_state_free(bvp);
     if (lqws) ocs::lq_workspace_free(lqws);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -358,6 +363,12 @@ inline GridDesc describe(const ocs_integrator_s* g) {
   d.lqws = const_cast<LqWorkspace**>(&g->lqws);
   return d;
 }
+
+// pieces of the sweep's workspace that bvp_solver's post-processing shares (ocs_fbs.cpp): the pchip node tables of the grid,
+// and interval index / local coordinate / time of the points linspace(T0, TF, nq)
+int fbs_ensure_tables(ocs_integrator_s* g);
+FbsTables fbs_tables(const ocs_integrator_s* g);
+int fbs_build_points(ocs_integrator_s* g, int nq, DevBuf& K, DevBuf& S, DevBuf& T);
 
 // make sure the time-coefficient table of (g, p) is current; enqueued on `s`
 inline int bind_problem(ocs_integrator_s* g, ocs_problem_s* p, int batch, hipStream_t s) {

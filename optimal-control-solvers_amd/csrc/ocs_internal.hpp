@@ -350,6 +350,58 @@ int launch_fbs_init(int batch, int nsweeps, int* usel, int* status, double* maxC
 int launch_fbs_advance(int batch, int sweep, int nparts, const double* metric, int* anyvalid, int* usel, int* status,
                        double* maxChange, int* nactive, hipStream_t s, const int* gate = nullptr);
 
+// batched bvp_solver (ocs_bvp_kernels.hip): damped Newton on the collocated optimality system, y = [x; lam] [N+1][2 nS][B]
+bool bvp_supported(const ProblemDesc& p);   // registry logistic family and user problems, nS <= 4, nC <= 2
+int bvp_chunks(int N);                      // rows of the partial-norm arrays SS, MX [chunks][B]
+struct BvpIterate {
+  int batch;
+  const double* x0;    // [nS][B]
+  const double* y;     // the iterate
+  const double* d;     // the Newton step (launch_bvp_norm: the residual is taken at y + alpha d)
+  double alpha;
+  const int* status;   // [B] 0 active, 1 converged, 2 failed: launch_bvp_assemble skips the finished instances
+  const int* search;   // [B] launch_bvp_norm skips instances with search == 0
+  double* AB;          // [N][2 nS (2 nS + 1)][B] step maps [A_i | b_i] (launch_bvp_assemble)
+  double* SS;          // [chunks][B] partial sums of squares of the residual (launch_bvp_norm) ...
+  double* MX;          //             ... and partial maxima of its magnitude
+  const int* gate;     // optional device flag: the launch does nothing if *gate == 0
+};
+int launch_bvp_assemble(const ProblemDesc& p, const GridDesc& g, const BvpIterate& a, hipStream_t s);
+int launch_bvp_norm(const ProblemDesc& p, const GridDesc& g, const BvpIterate& a, hipStream_t s);
+struct BvpSweepArgs {
+  int N, batch, it;
+  const double* AB;
+  double* PP;          // [N+1][nS (nS + 1)][B] rows of [P_i | p_i]
+  const double* y;
+  const double* x0;
+  double* d;           // [N+1][2 nS][B]
+  int* status;         // a non-finite step: 2
+  int* search;         // 1 for the instances whose step the line search is to try
+  int* iters;          // = it for every instance the sweep ran for
+  double* alpha;       // = 0
+};
+int launch_bvp_sweep(int nS, const BvpSweepArgs& a, hipStream_t s);
+struct BvpVerdictArgs {
+  int batch, nparts;
+  const double* SS;
+  const double* MX;
+  double tol;          // NewtonTol
+  int* search;
+  int* status;
+  double* nrm2;        // [B] ||Phi||_2 of the iterate
+  double* resinf;      // [B] ||Phi||_inf of the iterate
+  double* alpha;       // [B] accepted step length of this iteration, 0: none (yet)
+  int* slot;           // device counter of the instances that go on (searching / iterating); zeroed by the caller
+};
+int launch_bvp_accept(const BvpVerdictArgs& a, bool init, double step, const int* gate, hipStream_t s);
+int launch_bvp_finish(const BvpVerdictArgs& a, int it, int max_iter, bool final, hipStream_t s);
+int launch_bvp_update(int rows, int batch, const double* alpha, const double* d, double* y, hipStream_t s);
+int launch_bvp_init(int batch, int* status, int* search, int* iters, double* alpha, hipStream_t s);
+int launch_bvp_pack(int npts, int nS, int batch, const double* xs, int ldx, bool xs_nodes, const double* lam, double* y,
+                    hipStream_t s);
+int launch_bvp_costate_rows(int npts, int nS, int batch, const double* y, double* lam, hipStream_t s);
+int launch_bvp_converged(int batch, const int* status, int* converged, hipStream_t s);
+
 // registry queries (host)
 bool functor_supported(Functor f, int nS, int nC);
 int functor_ntc(Functor f, int nS);

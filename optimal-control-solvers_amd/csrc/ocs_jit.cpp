@@ -71,7 +71,7 @@ static Rtc* rtc() {
 
 int user_chunk(int nS) { return nS <= 4 ? 4 : 1; }
 
-static std::vector<std::string> kernel_names(int nS, int nC, bool rowsep, bool fold) {
+static std::vector<std::string> kernel_names(int nS, int nC, bool rowsep, bool fold, bool has_cc) {
   const std::string ch = std::to_string(user_chunk(nS));
   std::vector<std::string> n(UK_COUNT);
   n[UK_TCOEF] = "ocs::k_tcoef<ocs::UserP>";
@@ -119,6 +119,10 @@ static std::vector<std::string> kernel_names(int nS, int nC, bool rowsep, bool f
     n[UK_VSCAN_LAM_LT] = "ocs::k_backward_vscan<ocs::UserP, " + vw + ", true, false, true>";
     n[UK_VSCAN_DJDU_LT] = "ocs::k_backward_vscan<ocs::UserP, " + vw + ", false, true, true>";
     n[UK_COSTATE_VSCAN] = "ocs::k_costate_vscan<ocs::UserP, " + vw + ">";
+  }
+  if (has_cc && vector_shape_ok(nS, nC)) {   // (bvp_solver refuses a plugin without ocs_ControlChar)
+    n[UK_BVP_ASSEMBLE] = "ocs::k_bvp_assemble<ocs::UserP>";
+    n[UK_BVP_NORM] = "ocs::k_bvp_norm<ocs::UserP>";
   }
   return n;
 }
@@ -263,20 +267,22 @@ int jit_build(const char* user_src, int nS, int nC, int npar, bool has_cc, bool 
   if (fold) src += "#include \"ocs_fold_kernel.hpp\"\n";
   const bool vec = !rowsep && vector_shape_ok(nS, nC);
   if (vec) src += "#include \"ocs_pipelinev_kernel.hpp\"\n#include \"ocs_vscan_kernel.hpp\"\n#include \"ocs_costate_vscan_kernel.hpp\"\n";
+  if (has_cc && vector_shape_ok(nS, nC)) src += "#include \"ocs_bvp_device.hpp\"\n";
 
   const char* hdr_src[] = {src_ocs_device_common_hpp, src_ocs_user_functor_hpp, src_ocs_rk4_kernels_hpp,
                            src_ocs_fbs_device_hpp, src_ocs_pipeline2_kernel_hpp, src_ocs_scan_kernel_hpp,
                            src_ocs_pipelinev_kernel_hpp, src_ocs_vscan_kernel_hpp, src_ocs_fold_kernel_hpp,
                            src_ocs_costate_scan_kernel_hpp, src_ocs_costate_vscan_kernel_hpp,
-                           src_ocs_pipeline2_body_inc, src_ocs_scan_body_inc};
+                           src_ocs_pipeline2_body_inc, src_ocs_scan_body_inc, src_ocs_bvp_device_hpp};
   const char* hdr_name[] = {"ocs_device_common.hpp", "ocs_user_functor.hpp", "ocs_rk4_kernels.hpp",
                             "ocs_fbs_device.hpp", "ocs_pipeline2_kernel.hpp", "ocs_scan_kernel.hpp",
                             "ocs_pipelinev_kernel.hpp", "ocs_vscan_kernel.hpp", "ocs_fold_kernel.hpp",
                             "ocs_costate_scan_kernel.hpp", "ocs_costate_vscan_kernel.hpp",
-                            "ocs_pipeline2_body.inc", "ocs_scan_body.inc"};   // (the two kernels' shared bodies)
+                            "ocs_pipeline2_body.inc", "ocs_scan_body.inc",   // (the two kernels' shared bodies)
+                            "ocs_bvp_device.hpp"};
   constexpr int kNumHdr = sizeof(hdr_src) / sizeof(hdr_src[0]);
   static_assert(kNumHdr == sizeof(hdr_name) / sizeof(hdr_name[0]), "one name per header");
-  const std::vector<std::string> names = kernel_names(nS, nC, rowsep, fold);
+  const std::vector<std::string> names = kernel_names(nS, nC, rowsep, fold, has_cc);
   // Compiled code is kept for the life of the process, keyed by the full generated source (the kernel headers are fixed
   // per build of the library): creating the same problem again -- parameter studies, a test suite -- costs a module load
   // instead of 5-6 s of hipRTC.

@@ -36,6 +36,8 @@ enum UserKernel : int {
   UK_BWD_LAM_DJDU_XRC,
   // nS <= 4 with ocs_ControlChar: the error-point mode of fb_sweep by runs of intervals (k_control_pts_sorted)
   UK_CONTROL_PTS_SORTED,
+  // nS <= 4, nC <= 2: assembly and residual of the batched bvp_solver (ocs_bvp_device.hpp)
+  UK_BVP_ASSEMBLE, UK_BVP_NORM,
   UK_COUNT
 };
 

@@ -382,3 +382,59 @@ def single_shooting_batch(prob, x0, tspan, nCONTROL_PTS, Control=None, Integrato
 
     out["soln_of"] = soln_of
     return out
+
+
+def bvp_solver_batch(prob, x0, tspan, options=None, integrator=None):
+    """Batch bvp_solver (functions/bvp_solver.m:1-134): x0 is nS x batch (instances may also differ through
+    prob.set_batch_params / set_batch_bounds).  The optimality system y' = optSys(t, y), y = [x; lam], x(T0) = x0,
+    lam(TF) = 0 is collocated with bvp4c's Simpson formula on the nodes of `tspan` -- a fixed mesh: results are
+    grid-dependent -- and solved per instance by a damped Newton iteration on the device (ocs_bvp_solver).
+    options (a dict): y0 (the guess: 2nS x (N+1) [x batch] samples on tspan, or a callable t -> 2nS x k), else u0 (a control
+    guess as fb_sweep_batch takes it; the start is compute_x_lam under it), else the constant [x0; 0] (:87-98);
+    nINTERP_PTS (:20), NewtonTol (1e-10), MaxIter (40), maxBacktracks.
+    Returns a dict of sample arrays: y (2nS x (N+1) x batch, the collocation solution), u (nC x nINTERP x batch on
+    interpPts, :124-126), x, lam (nS x (N+1) x batch) and J from compute_x_lam_J under pchip(u) (:132), iterations,
+    converged, resnorm (||Phi||_inf per instance), status, tspan, interpPts."""
+    from ._lib import BvpOptions, ip
+    from .sweep import _sample_u0, matlab_linspace
+    options = dict(options or {})
+    o = BvpOptions()
+    check(lib.ocs_bvp_default_options(C.byref(o)))
+    for k in ("NewtonTol", "MaxIter", "maxBacktracks", "nINTERP_PTS"):
+        if k in options:
+            setattr(o, k, options[k])
+    # bvpRelTol / bvpAbsTol / MAX_MESH_SIZE (:15-19) steer bvp5c's error control and mesh adaptation, RelTol / AbsTol the
+    # adaptive odevr7 of compute_x_lam: here the mesh is tspan and the passes are fixed-step -- say so, as fb_sweep_batch does
+    ignored = [k for k in ("bvpRelTol", "bvpAbsTol", "MAX_MESH_SIZE", "RelTol", "AbsTol") if k in options]
+    if ignored:
+        import warnings
+        warnings.warn(f"bvp_solver: {', '.join(ignored)} steer the reference's adaptive solvers (bvp5c's mesh, odevr7) and "
+                      "have no effect here: the collocation mesh is tspan and Newton stops at NewtonTol (refine tspan for "
+                      "accuracy)", RuntimeWarning, stacklevel=2)
+    integ = integrator or RK4Integrator(tspan)
+    N = integ.nSTEPS
+    nS, nC = prob.nS, prob.nC
+    x0 = _f(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
+    if x0.shape[0] != nS:
+        x0 = _f(x0.reshape(nS, -1))
+    batch = x0.shape[1]
+    interpPts = matlab_linspace(integ.t[0], integ.t[-1], o.nINTERP_PTS)           # :99
+    y0 = u0g = None
+    if "y0" in options:                                                          # :91-93
+        g = options["y0"]
+        a = np.asarray(g(integ.tspan) if callable(g) else g, dtype=np.float64)
+        if a.ndim == 2:
+            a = np.repeat(a.reshape(2 * nS, N + 1)[:, :, None], batch, axis=2)
+        y0 = _f(a, (2 * nS, N + 1, batch))
+    elif "u0" in options:                                                        # :94-97
+        (u0g,) = _sample_u0(options["u0"], prob, [integ.t], batch)
+    y = np.empty((2 * nS, N + 1, batch), order="F")
+    x = np.empty((nS, N + 1, batch), order="F")
+    lam = np.empty((nS, N + 1, batch), order="F")
+    uI = np.empty((nC, o.nINTERP_PTS, batch), order="F")
+    J, res = np.empty(batch), np.empty(batch)
+    iters, conv = np.zeros(batch, dtype=np.int32), np.zeros(batch, dtype=np.int32)
+    status = check(lib.ocs_bvp_solver(integ._h, prob._h, batch, _p(x0), C.byref(o), _p(y0), _p(u0g), _p(y), _p(x), _p(lam),
+                                      _p(uI), _p(J), iters.ctypes.data_as(ip), conv.ctypes.data_as(ip), _p(res)))
+    return {"x": x, "lam": lam, "u": uI, "J": J, "y": y, "iterations": iters, "converged": conv.astype(bool),
+            "resnorm": res, "status": status, "tspan": integ.tspan, "interpPts": interpPts}
