@@ -84,14 +84,23 @@ def constant_guess(prob, x0, tspan):
     return np.vstack([np.repeat(x0[:, None], n, axis=1), np.zeros((prob.nS, n))])
 
 
-def solve(prob, x0, tspan, y0=None, NewtonTol=1e-10, MaxIter=40, maxBacktracks=12):
+def solve(prob, x0, tspan, y0=None, NewtonTol=1e-10, MaxIter=40, maxBacktracks=12, trace=False, jacobian=jacobian):
     """Damped Newton from y0 (default: the constant guess).  Returns a dict: y, converged, iterations, resnorm
-    (||Phi||_inf of y) and why it stopped."""
+    (||Phi||_inf of y) and why it stopped.  With `trace` also "trace": one dict per iteration with the iterate y after it,
+    the accepted step length alpha (0.0 where the iteration failed and left y as it was) and resinf, res2 = ||Phi(y)||_inf,
+    ||Phi(y)||_2; and "start": the same of y0 (alpha None).  `jacobian` replaces the Newton matrix (the tests of the twin
+    pass deliberately wrong ones to show that their bounds notice)."""
     nY = 2 * prob.nS
     y = constant_guess(prob, x0, tspan) if y0 is None else np.array(y0, dtype=np.float64).reshape(nY, -1)
     r = residual(prob, x0, tspan, y)
     nrm = float(np.sqrt(np.sum(r * r)))
     out = {"iterations": 0, "converged": False, "why": "MaxIter"}
+    steps = []
+
+    def note(alpha):
+        return {"y": y.copy(), "alpha": alpha, "resinf": float(np.max(np.abs(r))), "res2": nrm}
+
+    start = note(None)
     if not np.isfinite(nrm):
         out["why"] = "non-finite start"
     elif np.max(np.abs(r)) <= NewtonTol:
@@ -104,9 +113,11 @@ def solve(prob, x0, tspan, y0=None, NewtonTol=1e-10, MaxIter=40, maxBacktracks=1
                     d = np.linalg.solve(jacobian(prob, x0, tspan, y), -r)
             except np.linalg.LinAlgError:
                 out["why"] = "singular"
+                steps.append(note(0.0))
                 break
             if not np.all(np.isfinite(d)):
                 out["why"] = "non-finite step"
+                steps.append(note(0.0))
                 break
             d = d.reshape(-1, nY).T
             a, taken = 1.0, False
@@ -118,6 +129,7 @@ def solve(prob, x0, tspan, y0=None, NewtonTol=1e-10, MaxIter=40, maxBacktracks=1
                     y, r, nrm, taken = y + a * d, rt, nt, True
                     break
                 a *= 0.5
+            steps.append(note(a if taken else 0.0))
             if not taken:
                 out["why"] = "line search"
                 break
@@ -125,4 +137,17 @@ def solve(prob, x0, tspan, y0=None, NewtonTol=1e-10, MaxIter=40, maxBacktracks=1
                 out["converged"], out["why"] = True, "NewtonTol"
                 break
     out["y"], out["resnorm"] = y, float(np.max(np.abs(r)))
+    if trace:
+        out["trace"], out["start"] = steps, start
     return out
+
+
+def step_noise(prob, x0, tspan, y, **options):
+    """The twin's own sensitivity to a last-bit change of its input: one damped Newton step (solve with MaxIter = 1) from y
+    and one from nextafter(y, inf); the largest difference of the two results.  The forward-difference quotient divides
+    rounding errors of optSys by sqrt(eps) max(1, |y|), so this is far above one ulp, and no comparison of two float64
+    implementations of the step can ask for less."""
+    y = np.asarray(y, dtype=np.float64)
+    a = solve(prob, x0, tspan, y0=y, **dict(options, MaxIter=1))["y"]
+    b = solve(prob, x0, tspan, y0=np.nextafter(y, np.inf), **dict(options, MaxIter=1))["y"]
+    return float(np.max(np.abs(a - b)))
