@@ -50,8 +50,8 @@ __global__ __launch_bounds__(W * 64) void k_costate_vscan(const CostateScanArgs 
     const int lo = chunk_lo(sb);
     const int lr = lo >= 0 ? lo : -kScanPadFront;                       // records lo .. lo+7 (zero records below step 0)
     const int lp = lo < 0 ? 0 : (lo > N - 8 ? N - 8 : lo);              // interval records lp .. lp+7, inside the table
-    dma16_sc(a.RECS + (long long)lr * kScanRec + 2 * lane, &tab[slot][wave][0][0]);
-    dma16_sc(a.PR + (size_t)lp * kPRec + 2 * lane, &tab[slot][wave][1][0]);
+    dma16(a.RECS + (long long)lr * kScanRec + 2 * lane, &tab[slot][wave][0][0]);
+    dma16(a.PR + (size_t)lp * kPRec + 2 * lane, &tab[slot][wave][1][0]);
 #pragma unroll
     for (int t = 0; t < L + 3; ++t) {
       int i = lo - 1 + t;
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(W * 64) void k_costate_vscan(const CostateScanArgs 
       sm[sb & 1][wave][NS * NS + i][lane] = bv[i];
     }
     load(sb + 1, dn, slot ^ 1);
-    lds_barrier_sc();
+    lds_barrier();
     // ---------------- phase 2: lam at the top of this chunk ----------------
     double lam[NS];
 #pragma unroll

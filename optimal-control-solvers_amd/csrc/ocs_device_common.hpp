@@ -10,6 +10,26 @@ namespace ocs {
 
 #define OCS_INLINE __attribute__((always_inline))
 
+// ---------------------------------------------------------------------------------------
+// wave primitives: THE copy for every kernel translation unit and the hipRTC header set
+// ---------------------------------------------------------------------------------------
+// Hand-off barrier: only LDS traffic has to be complete.  __syncthreads() would also drain vmcnt,
+// i.e. every global store still in flight.
+__device__ static inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// 16-byte-per-lane LDS-DMA: lane l copies src_l[0..1] to lds_base[2l..2l+1]
+__device__ static inline void dma16(const double* src, double* lds_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
+}
+// fp64 cross-lane move inside a quad (DPP quad_perm on the two 32-bit halves)
+template <int CTRL>
+__device__ static inline double dpp_quad(double v) {
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  const int lo2 = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
+  const int hi2 = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi2, lo2);
+}
+
 // First trajectory of a workgroup's tile of TPW trajectories.  A batch that is not a multiple of the tile: the LAST workgroup takes
 // the last TPW trajectories, overlapping its neighbour -- the overlap is computed twice with the same operations (the tiled
 // kernels accumulate nothing across trajectories).  A kernel that writes only arrays it does not read (the state passes: x, J from

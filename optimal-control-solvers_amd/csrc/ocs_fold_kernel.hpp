@@ -118,16 +118,16 @@ __global__ __launch_bounds__(FoldCfg<P::NS>::NWAVE * 64) void k_forward_cc(const
       double* dst = &inp[0][0] + cI * C_::SLOT;
       cI = cI + 1 == NSLOT ? 0 : cI + 1;
       const int jt = j < nb ? j : nb - 1;
-      dma16_p2(a.REC + (size_t)jt * C_::REC_DBL + 2 * lane, dst);
+      dma16(a.REC + (size_t)jt * C_::REC_DBL + 2 * lane, dst);
 #pragma unroll
       for (int q = 0; q < C_::NLAM; ++q) {
         const int e = q * 128 + 2 * lane, st = e / 64, rr = (e % 64) / TPW, t2 = e % TPW;
         const int node = j * D + st < N ? j * D + st : N;
-        dma16_p2(a.lam + ((size_t)node * G + rr) * B + bw + t2, dst + C_::LOFF + q * 128);
+        dma16(a.lam + ((size_t)node * G + rr) * B + bw + t2, dst + C_::LOFF + q * 128);
       }
       if constexpr (C_::PRL) {
-        dma16_p2(a.PR + (size_t)jt * C_::PR_DBL + 2 * lane, dst + C_::POFF);
-        if (lane < C_::TU_DBL / 2) dma16_p2(a.TU + (size_t)jt * 2 * D + 2 * lane, dst + C_::TOFF);
+        dma16(a.PR + (size_t)jt * C_::PR_DBL + 2 * lane, dst + C_::POFF);
+        if (lane < C_::TU_DBL / 2) dma16(a.TU + (size_t)jt * 2 * D + 2 * lane, dst + C_::TOFF);
       }
     };
     // before barrier k the blocks <= k+4 have landed

@@ -389,7 +389,6 @@ __global__ __launch_bounds__(64) void k_backward_fc(const FcArgs a) {
 // bit-identical to k_forward_fc / k_backward_fc.  Requires N % 8 == 0 and nBasis <= 16.
 // ---------------------------------------------------------------------------------------
 constexpr int kFc2Steps = 8;  // steps per block
-__device__ static inline void fc2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // the basis wave's half of a block: the NR samples u(:,j) of the basis columns src[0..NR) into one LDS slot
 template <int NC, int NR>
@@ -441,15 +440,15 @@ __global__ __launch_bounds__(128) void k_forward_fc2(const FcArgs a) {
     load_rows(rb0);
     if (nblk > 1) load_rows(rb1);
     expand(rb0, 0);
-    fc2_barrier();
+    lds_barrier();
     for (int j = 0; j < nblk; j += 2) {
       if (j + 2 < nblk) load_rows(rb0);
       if (j + 1 < nblk) expand(rb1, 1);
-      fc2_barrier();
+      lds_barrier();
       if (j + 1 < nblk) {
         if (j + 3 < nblk) load_rows(rb1);
         if (j + 2 < nblk) expand(rb0, 0);
-        fc2_barrier();
+        lds_barrier();
       }
     }
     return;
@@ -498,7 +497,7 @@ __global__ __launch_bounds__(128) void k_forward_fc2(const FcArgs a) {
     recp += rec_stride(NTC);
   }
   auto next_rec = [&]() OCS_INLINE { return rec_ring_next<NTC, PF, 1>(rq, recp); };
-  fc2_barrier();
+  lds_barrier();
   double uprev[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) uprev[c] = u0s[c][lane];
@@ -516,7 +515,7 @@ __global__ __launch_bounds__(128) void k_forward_fc2(const FcArgs a) {
 #pragma unroll
       for (int c = 0; c < NC; ++c) uprev[c] = us[2 * s + 1][c];
     }
-    fc2_barrier();
+    lds_barrier();
   }
   if (b0 < a.batch) a.J[b] = yc;  // J = x(end,end)   :55
   if (warm == 1.234567e300) a.J[b] = warm;
@@ -573,19 +572,19 @@ __global__ __launch_bounds__(128) void k_backward_fc2(const FcArgs a) {
     load_rows(E0, 0, 0);
     if (nblk > 1) load_rows(E1, 1, 0);
     expand(E0, 0);
-    fc2_barrier();
+    lds_barrier();
     for (int t = 0; t < nblk; t += 2) {
       if (t + 2 < nblk) load_rows(E0, t + 2, 0);
       load_rows(C0, t, 1);
       if (t + 1 < nblk) expand(E1, 1);
       if (t >= 1) contract(C1, 1);
-      fc2_barrier();
+      lds_barrier();
       if (t + 1 < nblk) {
         if (t + 3 < nblk) load_rows(E1, t + 3, 0);
         load_rows(C1, t + 1, 1);
         if (t + 2 < nblk) expand(E0, 0);
         contract(C0, 0);
-        fc2_barrier();
+        lds_barrier();
       }
     }
     if ((nblk - 1) & 1) contract(C1, 1); else contract(C0, 0);
@@ -713,11 +712,11 @@ __global__ __launch_bounds__(128) void k_backward_fc2(const FcArgs a) {
 #pragma unroll
       for (int c = 0; c < NC; ++c) ends[1][c][lane] = pend[c];
     }
-    fc2_barrier();
+    lds_barrier();
   };
   double xb0[BS][NS], xb1[BS][NS];
   load_xs(xb0);
-  fc2_barrier();
+  lds_barrier();
 #pragma unroll
   for (int c = 0; c < NC; ++c) unext[c] = ends[0][c][lane];
   for (int t = 0; t < nblk; t += 2) {

@@ -55,7 +55,7 @@ __device__ static inline void swap32_fw(double a, double& lower, double& upper) 
   upper = __hiloint2double((int)hi[1], (int)lo[1]);
 }
 
-// 16-byte-per-lane LDS-DMA as dma16_sc, issued from inline assembly.  The compiler orders every later LDS read behind the
+// 16-byte-per-lane LDS-DMA as dma16 (ocs_device_common.hpp), issued from inline assembly.  The compiler orders every later LDS read behind the
 // LDS-DMA instructions it knows about once there are more than a few of them in flight (a vmcnt(0) right behind their
 // issue: the whole memory latency, every superblock); the kernel below waits for its DMAs itself, one superblock later.
 __device__ static inline void dma16_fw(const double* src, const double* lds_dst) {
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(W * 64, (NKS > 4 ? 1024 : 2048) / (W * 64)) void k_
     const double EB = g == 0 ? 0.0 : g == 1 ? eB : g == 2 ? p01B : e3B;
     if (g == 0) sm[sb & 1][wave][n] = double2{TA, TB};
     FCS_T(3);   // maps inside the wave
-    lds_barrier_sc();
+    lds_barrier();
     FCS_T(4);   // barrier
     // ---------------- phase 2: lam at the top of this chunk ----------------
     double lam = (sb == 0) ? 0.0 : csm[(sb & 1) ^ 1][n];

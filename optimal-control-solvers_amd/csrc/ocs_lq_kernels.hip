@@ -387,7 +387,7 @@ constexpr int kX2Pair = 64, kX2Wave = 3 * kX2Pair, kX2Slot = 2 * kX2Wave;  // d2
 
 __device__ static inline void lq_lds_barrier() {
   __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  lds_barrier();
   __builtin_amdgcn_sched_barrier(0);
 }
 

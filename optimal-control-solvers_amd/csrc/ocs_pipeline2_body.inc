@@ -32,7 +32,7 @@
       cI = cI + 1 == NSLOT ? 0 : cI + 1;
 #pragma unroll
       for (int q = 0; q < C_::NREC; ++q)
-        dma16_p2(a.REC + (size_t)j * C_::REC_DBL + q * 128 + 2 * lane, dst + q * 128);
+        dma16(a.REC + (size_t)j * C_::REC_DBL + q * 128 + 2 * lane, dst + q * 128);
 #pragma unroll
       for (int q = 0; q < C_::NU && NKS == 0; ++q) {
         OCS_P2_DMA_U(j, q, dst)

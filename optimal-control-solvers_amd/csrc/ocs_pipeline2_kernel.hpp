@@ -35,19 +35,14 @@ namespace ocs {
 #ifdef OCS_P2_STAMPS
 __device__ static long long g_p2_stamp[16 * 4];   // per wave role: {barrier wait, total, -, -} of workgroup 0
 __device__ static long long g_p2_wg[1024 * 4];    // per workgroup: S wave {start, end, barrier wait, xcc}
-#define P2_BARRIER() do { const long long t0_ = __builtin_amdgcn_s_memtime(); lds_barrier_p2_(); tbar_ += __builtin_amdgcn_s_memtime() - t0_; } while (0)
+#define P2_BARRIER() do { const long long t0_ = __builtin_amdgcn_s_memtime(); lds_barrier(); tbar_ += __builtin_amdgcn_s_memtime() - t0_; } while (0)
 #define P2_BEGIN() long long tbar_ = 0; const long long tstart_ = __builtin_amdgcn_s_memtime(); const long long rstart_ = __builtin_amdgcn_s_memrealtime()
 #define P2_END(w) do { if (blockIdx.x == 0 && lane == 0) { g_p2_stamp[(w) * 4] = tbar_; g_p2_stamp[(w) * 4 + 1] = __builtin_amdgcn_s_memtime() - tstart_; } if ((w) == 1 && lane == 0 && blockIdx.x < 1024) { g_p2_wg[blockIdx.x * 4] = tstart_; g_p2_wg[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memtime(); g_p2_wg[blockIdx.x * 4 + 2] = rstart_; g_p2_wg[blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memrealtime() - rstart_; } } while (0)
 #else
-#define P2_BARRIER() lds_barrier_p2_()
+#define P2_BARRIER() lds_barrier()
 #define P2_BEGIN()
 #define P2_END(w)
 #endif
-__device__ static inline void lds_barrier_p2_() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ static inline void dma16_p2(const double* src, double* lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 // wait until at most `blocks` * LPB of this wave's vector-memory operations are outstanding (blocks is wave-uniform)
 template <int LPB, int QMAX>
 __device__ static inline void wait_blocks_p2(int blocks) {
@@ -180,7 +175,7 @@ __global__ __launch_bounds__((P2Cfg<P::NS, NKS, TPW_>::NWAVE * 64)) void k_forwa
 #define OCS_P2_U0(b, lu) b
 #define OCS_P2_DMA_U(j, q, dst)                                  \
   const int e = q * 128 + 2 * lane, row = e / TPW, t2 = e % TPW; \
-  dma16_p2(a.u + ((size_t)(2 * D * j + 1 + row)) * B + bw + t2, dst + C_::REC_DBL + q * 128);
+  dma16(a.u + ((size_t)(2 * D * j + 1 + row)) * B + bw + t2, dst + C_::REC_DBL + q * 128);
 #define OCS_P2_DROP(c) (c)
 #define OCS_P2_IF_TILE(c) c
 #define OCS_P2_IF_TRAJ(c) c
@@ -255,7 +250,7 @@ __global__ __launch_bounds__((P2Cfg<P::NS>::NWAVE * 64)) void k_forward_p2_tiled
 #define OCS_P2_DMA_U(j, q, dst)                                                                    \
   const int e = q * 128 + 2 * lane;                                                                \
   const int tq = e / (2 * D * kTile);                                                              \
-  dma16_p2(a.u + u0w + pos(tq * kTile).lu + (size_t)(2 * D * j + 1) * kTile + e % (2 * D * kTile), \
+  dma16(a.u + u0w + pos(tq * kTile).lu + (size_t)(2 * D * j + 1) * kTile + e % (2 * D * kTile), \
            dst + C_::REC_DBL + q * 128);
 #define OCS_P2_DROP(c) (c || !ps_.tv)
 #define OCS_P2_IF_TILE(c) c && ps_.tv

@@ -31,24 +31,7 @@
 
 namespace ocs {
 
-
-template <int CTRL>
-__device__ static inline double dpp_quad_pl(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const int lo2 = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  const int hi2 = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi2, lo2);
-}
-
-// Hand-off barrier: only LDS traffic has to be complete.  __syncthreads() would also drain vmcnt,
-// i.e. every global store still in flight.
-__device__ static inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 16-byte-per-lane LDS-DMA: lane l copies src_l[0..1] to lds_base[2l..2l+1]
-__device__ static inline void dma16(const double* src, double* lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
+// (lds_barrier, dma16, dpp_quad: ocs_device_common.hpp)
 // wait until at most `blocks` * LPB of this wave's vector-memory operations are outstanding, i.e.
 // until every DMA except those of the youngest `blocks` blocks has landed (blocks is wave-uniform)
 template <int LPB>
@@ -348,19 +331,19 @@ __global__ __launch_bounds__(256) void k_backward_pl(const BwdArgsPL a) {
               S4 += c.k4[q];
             }
             // the node above this step: its control and its B'k1 sit in the lane of the step processed just before
-            const double un_s = (G == 1) ? ucar : dpp_quad_pl<(G == 4) ? 0x90 : 0xA0>(c.uA);
+            const double un_s = (G == 1) ? ucar : dpp_quad<(G == 4) ? 0x90 : 0xA0>(c.uA);
             const double unext = csub ? un_s : ucar;
             const double p1 = P::row_dfdu(cws * c.uA, S1, ev1);
             const double p4 = P::row_dfdu(cws * unext, S4, ev4);
             const double cuM = cws * c.uM;
             const double p23 = P::row_dfdu(cuM + cuM, S23, ev3);  // (cuM ev3 - k2) + (cuM ev3 - k3)
-            const double p1_s = (G == 1) ? pend : dpp_quad_pl<(G == 4) ? 0x90 : 0xA0>(p1);
+            const double p1_s = (G == 1) ? pend : dpp_quad<(G == 4) ? 0x90 : 0xA0>(p1);
             const double pabove = csub ? p1_s : pend;
             double* dp = a.dJdu + (size_t)(2 * i + 2) * B + bx;
             __builtin_nontemporal_store(pabove + p4, dp);   // column 2i+2 (non-temporal: see ocs_scan_kernels.hip)
             __builtin_nontemporal_store(p23, dp - B);       // column 2i+1
-            pend = (G == 1) ? p1 : dpp_quad_pl<(G == 4) ? 0xFF : 0xF5>(p1);
-            ucar = (G == 1) ? c.uA : dpp_quad_pl<(G == 4) ? 0xFF : 0xF5>(c.uA);
+            pend = (G == 1) ? p1 : dpp_quad<(G == 4) ? 0xFF : 0xF5>(p1);
+            ucar = (G == 1) ? c.uA : dpp_quad<(G == 4) ? 0xFF : 0xF5>(c.uA);
           }
         }
       }

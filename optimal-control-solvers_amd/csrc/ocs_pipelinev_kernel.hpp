@@ -60,12 +60,12 @@ __global__ __launch_bounds__((PVCfg<P::NS, P::NC>::NWAVE * 64)) void k_forward_p
       cI = cI + 1 == NSLOT ? 0 : cI + 1;
 #pragma unroll
       for (int q = 0; q < C_::NREC; ++q)
-        dma16_p2(a.REC + (size_t)j * C_::REC_DBL + q * 128 + 2 * lane, dst + q * 128);
+        dma16(a.REC + (size_t)j * C_::REC_DBL + q * 128 + 2 * lane, dst + q * 128);
 #pragma unroll
       for (int q = 0; q < C_::NU; ++q) {
         // piece q: 128 doubles = two rows of 64 lanes; a lane copies two consecutive trajectories of one row
         const int e = q * 128 + 2 * lane, row = e / 64, t2 = e % 64;   // row = sample * NC + control
-        dma16_p2(a.u + ((size_t)(2 * D * j + 1) * NC + row) * B + bw + t2, dst + C_::REC_DBL + q * 128);   // (whole tiles)
+        dma16(a.u + ((size_t)(2 * D * j + 1) * NC + row) * B + bw + t2, dst + C_::REC_DBL + q * 128);   // (whole tiles)
       }
     };
     auto prepare = [&](int j) OCS_INLINE {   // block j has landed: the node before its first step, for the objective waves
@@ -83,7 +83,7 @@ __global__ __launch_bounds__((PVCfg<P::NS, P::NC>::NWAVE * 64)) void k_forward_p
       if (nb > 1) prepare(1);
     }
     for (int k = -1; k <= nb + 1; ++k) {
-      lds_barrier_p2_();
+      lds_barrier();
       if (k < 0) continue;
       if (k + 1 + Q < nb) issue(k + 1 + Q);
       if (k + 2 < nb) {
@@ -102,7 +102,7 @@ __global__ __launch_bounds__((PVCfg<P::NS, P::NC>::NWAVE * 64)) void k_forward_p
     for (int c = 0; c < NC; ++c) uprev[c] = a.u[(size_t)c * B + b];
     int cS = 0;
     for (int k = -1; k <= nb + 1; ++k) {
-      lds_barrier_p2_();
+      lds_barrier();
       if (k >= 0 && k < nb) {
         const double* rec = &inp[0][0] + cS * C_::SLOT;
         cS = cS + 1 == NSLOT ? 0 : cS + 1;
@@ -152,7 +152,7 @@ __global__ __launch_bounds__((PVCfg<P::NS, P::NC>::NWAVE * 64)) void k_forward_p
     const unsigned vx = (valid && !fz) ? (unsigned)((size_t)b * 8) : kDropP2;
     int cC = 0;
     for (int k = -1; k <= nb + 1; ++k) {
-      lds_barrier_p2_();
+      lds_barrier();
       if (k >= 1 && k <= nb) {
         const int j = k - 1;
         const double* rec = &inp[0][0] + cC * C_::SLOT;
@@ -201,7 +201,7 @@ __global__ __launch_bounds__((PVCfg<P::NS, P::NC>::NWAVE * 64)) void k_forward_p
     double carry = 0.0;
     if (wc && valid && !fz) a.x[(size_t)NS * B + b] = 0.0;
     for (int k = -1; k <= nb + 1; ++k) {
-      lds_barrier_p2_();
+      lds_barrier();
       if (k >= 2) {
         const int j = k - 2;
         const BufP2 bx = BufP2::make(a.x + (size_t)(j * D) * colB);

@@ -19,15 +19,6 @@
 
 namespace ocs {
 
-
-// fp64 cross-lane move inside a quad (DPP quad_perm on the two 32-bit halves)
-template <int CTRL>
-__device__ static inline double dpp_quad(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const int lo2 = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  const int hi2 = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi2, lo2);
-}
 // sum over the G lanes of a group; every lane of the group gets the same bits
 template <int G>
 __device__ static inline double group_sum(double v) {

@@ -50,18 +50,16 @@
     double u[2 * L + 1];  // u(2 lo + k)
     double xb, ub0, ub1;  // DFDU_READS_Y only: x(r, lo-1), u(2 lo - 2), u(2 lo - 1) (stage state 4 of the step below)
   };
-  // chunk of wave `wave` in superblock sb: steps lo .. hi; below step 0 a chunk is dead as a whole (N % L == 0)
-  auto chunk_lo = [&](int sb) OCS_INLINE { return N - (sb * W + wave + 1) * L; };
   // The loads of a chunk in L parts (part q: the records with q = 0, x(lo+q), u(2 lo + 2q), u(2 lo + 2q + 1),
   // and u(2 lo + 2L) with the last part), so that they can be issued between the steps of the previous superblock's
   // arithmetic: sixteen waves issuing 14 loads each back to back fill the address queue and stall at issue.
   auto load_part = [&](int sb, Ld& d, int slot, int q) OCS_INLINE {
-    const int lo = chunk_lo(sb), lc = lo > 0 ? lo : 0;
+    const int lo = scan_chunk_lo<W, L>(N, sb, wave), lc = lo > 0 ? lo : 0;
     // the records first: older in the in-order queue than the loads the compiler waits for
     // (a dead chunk -- below step 0, possibly far below in a superblock past the horizon -- takes zero records
     //  from the front pad: identity maps)
     const int lr = lo >= 0 ? lo - 1 : -kScanPadFront;
-    if (q == 0) dma16_sc(a.RECS + (long long)lr * kScanRec + 2 * lane, &rcs[slot][wave][0]);
+    if (q == 0) dma16(a.RECS + (long long)lr * kScanRec + 2 * lane, &rcs[slot][wave][0]);
     const Buf bx = Buf::make(a.xck + OCS_SC_X0W (size_t)lc * colB), bu = Buf::make(a.u + OCS_SC_U0W (size_t)(2 * lc) * OCS_SC_RU);
     if (q == 0) d.x0 = bx.ld(vx, 0);
     d.u[2 * q] = bu.ld(vu, (unsigned)(2 * q) * B8);
@@ -88,7 +86,7 @@
   };
 
   auto process = [&](int sb, const Ld& d, int slot, bool first, Ld& dn) OCS_INLINE {
-    const int lo = chunk_lo(sb);
+    const int lo = scan_chunk_lo<W, L>(N, sb, wave);
     const bool live = lo >= 0, topc = lo + L == N;
     // the records have landed once everything up to this superblock's loads has (in-order vmcnt); younger: the
     // previous superblock's stores (the loads of the next superblock are issued inside phase 1, after this wait)
@@ -172,12 +170,8 @@
       __builtin_amdgcn_sched_barrier(0);
     }
     sm[sb & 1][wave][lane] = double2{A, Bq};
-    lds_barrier_sc();
+    lds_barrier();
     // ---------------- phase 2: lam at the top of this chunk ----------------
-    // lam at the top of the superblock: lamT for the first one, afterwards what the LAST wave of the previous
-    // superblock left at the bottom of its chunk (published to LDS behind its phase 3, i.e. before this superblock's
-    // barrier) -- so every wave composes only the maps of the chunks above its own, in groups of four (all W at once
-    // would hold 4 W registers), and superblock boundaries carry the serial recursion's own value.
     double lam = (sb == 0) ? carry : csm[(sb & 1) ^ 1][lane];
 #pragma unroll
     for (int j0 = 0; j0 < W; j0 += 4) {

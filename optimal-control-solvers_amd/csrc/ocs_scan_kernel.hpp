@@ -83,7 +83,6 @@ __device__ static inline double pair_sum_sc(double a, double b) {
   }
   return swap_add32(a, b);               // halves (= rows): [a0+a1, b0+b1]
 }
-__device__ static inline void lds_barrier_sc() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct BwdArgsScan {
   int N, batch;          // N: a multiple of L (the launcher gives the remainder to the lane kernel)
@@ -124,11 +123,6 @@ struct Buf {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_sc, v), r, voff, soff, 2);
   }
 };
-// 16-byte-per-lane LDS-DMA: lane l copies src_l[0..1] to lds_base[2l..2l+1]
-__device__ static inline void dma16_sc(const double* src, double* lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 
 constexpr int kScanRec = 16;       // doubles per record: {h, h/2, h/6, h/3 | s4, s3, s1, 0 | tcA, tcM, tcB, 0 | pad}
 constexpr int kScanPadFront = 136; // zero records before step 0 (>= the steps of a superblock + 1: 16 x 4 in
@@ -138,6 +132,14 @@ constexpr int kScanPadBack = 8;    // and after step N-1 (a wave copies 8 record
 // bytes of checkpoint traffic per (trajectory, step) instead of 8 nS, for four more evaluations of the row's right-hand
 // side.  Measured at BL-2 (batch 4096, nS = 4): buffers that rotate through HBM 94.5 -> 89.2 us, one buffer set re-used
 // from the memory-side cache 79.9 -> 81.0 us; nS = 1: 70.3 -> 66.8 / 69.2 -> 66.7 us (profiles/r04f_xrc.log; NOTES.md).
+
+// Chunk of wave `wave` in superblock sb of a scan over time: steps lo .. lo + L - 1, superblocks counted from the end of the
+// horizon.  Below step 0 a chunk is dead as a whole (N % L == 0).  Used by k_backward_scan(_tiled) and k_backward_vscan; the
+// costate scans keep a lambda with the same line, and the rest of what the four kernels have in common -- the phase 2 carry,
+// the dense map algebra, the pchip block, the clamped loads -- is the same text in each of them ON PURPOSE: as shared
+// functions each of these changed the kernels' code (NOTES.md, "Scan kernels: wave primitives once").
+template <int W, int L>
+__device__ constexpr int scan_chunk_lo(int N, int sb, int wave) { return N - (sb * W + wave + 1) * L; }
 
 // The kernel body is ONE text, ocs_scan_body.inc, included into k_backward_scan and into k_backward_scan_tiled below.  The spots
 // that depend on the device layout are OCS_SC_ macros, defined before each #include and gone after it:

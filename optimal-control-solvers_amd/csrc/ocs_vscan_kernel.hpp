@@ -73,11 +73,10 @@ __global__ __launch_bounds__(W * 64) void k_backward_vscan(const BwdArgsScan a) 
     double u[2 * L + 1][NC];
     double xb[NS], ub0[NC], ub1[NC];   // stage state 4 of the step below the chunk (its B'k4 belongs to column 2 lo)
   };
-  auto chunk_lo = [&](int sb) OCS_INLINE { return N - (sb * W + wave + 1) * L; };
   auto load_part = [&](int sb, Ld& d, int slot, int q) OCS_INLINE {
-    const int lo = chunk_lo(sb), lc = lo > 0 ? lo : 0;
+    const int lo = scan_chunk_lo<W, L>(N, sb, wave), lc = lo > 0 ? lo : 0;
     const int lr = lo >= 0 ? lo - 1 : -kScanPadFront;
-    if (q == 0) dma16_sc(a.RECS + (long long)lr * kScanRec + 2 * lane, &rcs[slot][wave][0]);
+    if (q == 0) dma16(a.RECS + (long long)lr * kScanRec + 2 * lane, &rcs[slot][wave][0]);
     const Buf bx = Buf::make(a.xck + (size_t)lc * colB), bu = Buf::make(a.u + (size_t)(2 * lc) * NC * B);
 #pragma unroll
     for (int k = 0; k < NS; ++k) d.x[q][k] = bx.ld(vb, (unsigned)q * col8 + (unsigned)k * B8);
@@ -159,7 +158,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_vscan(const BwdArgsScan a) 
   };
 
   auto process = [&](int sb, const Ld& d, int slot, bool first, Ld& dn) OCS_INLINE {
-    const int lo = chunk_lo(sb);
+    const int lo = scan_chunk_lo<W, L>(N, sb, wave);
     const bool live = lo >= 0, topc = lo + L == N;
     if (first)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -224,7 +223,7 @@ __global__ __launch_bounds__(W * 64) void k_backward_vscan(const BwdArgsScan a) 
       for (int j = 0; j < NS; ++j) sm[sb & 1][wave][i * NS + j][lane] = M[i][j];
       sm[sb & 1][wave][NS * NS + i][lane] = bv[i];
     }
-    lds_barrier_sc();
+    lds_barrier();
     // ---------------- phase 2: lam at the top of this chunk ----------------
     double lam[NS];
 #pragma unroll

@@ -440,6 +440,38 @@ def _sym_logistic(ocs, nS):
     return g, f, vals
 
 
+@pytest.mark.parametrize("nS,N,batch", [(1, 8, 64), (1, 136, 128), (3, 8, 64), (3, 72, 128), (4, 8, 64), (4, 40, 128)])
+def test_fb_sweep_dense_map_costate_scan_at_one_three_and_four_states(ocs, oracle, nS, N, batch):
+    """k_costate_vscan's dense map algebra beyond two states: fb_sweep on the symbol-generated logistic plugin kept as
+    full-vector methods, against the registry problem of the same equations and, on instances 0, B/2 and B-1, the oracle.
+    Whole tiles of 64 (a ragged batch goes to the lane kernels).  N = 8: one superblock, most of its chunks dead;
+    N = 2 W L + 8 with the kernel's W (16, 8, 4 waves at 1, 3, 4 states) and L = 4: two full superblocks and a partial one, so
+    the carry goes through the LDS hand-over twice.  Error points on the nodes.  Horizon 2: on [0, 8] the undamped sweep
+    of fb_sweep.m:79-87 does not converge with four states (nor, at N = 8, with one) -- in the oracle as on the device."""
+    assert N in (8, 2 * {1: 16, 3: 8, 4: 4}[nS] * 4 + 8)
+    g, f, vals = _sym_logistic(ocs, nS)
+    m = [3.0, 2.5, 2.0, 1.5][:nS]
+    pu = ocs.make_from_symbolic(g, f, nS, 1, vals, BOUNDS, allow_rows=False)
+    assert pu.generated["form"] == "vector" and pu.generated["has_control_char"]
+    reg = ocs.LogisticProblem(m, 1.5, 0.05, BOUNDS)
+    rng = np.random.default_rng(1000 * nS + N + batch)
+    tspan = oracle.linspace(0, 2.0, N + 1)
+    x0 = rng.uniform(0.8, 1.6, (nS, batch))
+    opts = {"nERROR_PTS": N + 1, "nINTERP_PTS": 81}
+    gu, gr = ocs.RK4Integrator(tspan), ocs.RK4Integrator(tspan)
+    su = ocs.fb_sweep_batch(pu, x0, tspan, opts, integrator=gu)
+    sr = ocs.fb_sweep_batch(reg, x0, tspan, opts, integrator=gr)
+    assert ocs.fb_sweep_path(gu) == 2
+    assert np.array_equal(su["sweeps"], sr["sweeps"]) and np.all(su["sweeps"] > 0)
+    for k, tol in (("J", 1e-11), ("x", 1e-10), ("lam", 1e-10), ("u", 1e-10)):
+        assert relerr(su[k], sr[k]) < tol, k
+    po = oracle.LogisticProblem(m, 1.5, 0.05, BOUNDS)
+    for b in sorted({0, batch // 2, batch - 1}):
+        so = oracle.fb_sweep(po, x0[:, b], tspan, opts)
+        assert su["sweeps"][b] == so["_sweeps"] and abs(su["J"][b] - so["J"]) < 1e-10 * abs(so["J"])
+        assert relerr(su["lam"][:, :, b], so["lam"]) < 1e-10 and relerr(su["u"][:, :, b], so["u"]) < 1e-10
+
+
 @pytest.mark.parametrize("nS,rows", [(1, True), (2, True), (4, True), (2, False)])
 def test_problem_generated_from_symbols_equals_registry_problem(ocs, oracle, nS, rows):
     """TestOCProblem / LogisticK from their two symbolic expressions (make_from_symbolic.m:1-38): the generated plugin
