@@ -172,6 +172,8 @@ static int pipeline_steps(const ProblemDesc& p, int N, int batch, bool backward)
 }
 static bool forward_is_vector(const ProblemDesc& p) { return !pipeline_problem_ok(p) && vector_problem_ok(p); }
 // boundary: the caller's output arrays can carry the hand-over column of a split pass (x forward, lam backward)
+// Accuracy: MAP_PIPELINE's state pass rounds at the size of m_r/2 (recursion on z = y - m_r/2); states orders of magnitude below
+// that lose relative precision there and not on MAP_LANE / MAP_ROWSPLIT.  The choice below cannot see the states: DESIGN.md 3.
 static int choose_mapping(const ProblemDesc& p, int N, int batch, int requested, bool plain, bool backward,
                           bool boundary) {
   if (requested != MAP_AUTO) return requested;

@@ -23,7 +23,9 @@
 //   M: issues block k+1+Q, waits for block k+2    P: prepares block k+1    S: block k    C: block k-1    J: block k-2
 // Results: a step is the recursion on z and the objective summed over rows before the quadrature weights (DESIGN.md,
 // Numerics; generic row functions: the reference's sum, RK4Integrator.m:50) -- to round-off the lane kernels' and the
-// oracle's.  The state pass of the folded sweep (ocs_fold_kernel.hpp) repeats this arithmetic.
+// oracle's where the states are of the size of m_r/2.  The recursion on z rounds at the size of m_r/2, not of y: on a state
+// far below m_r/2 the relative error is up to (1 + m_r / (2 |y|)) times the plain recursion's ("Rounding error
+// per mapping"; tests/test_gpu_rk4_accuracy.py).  The state pass of the folded sweep (ocs_fold_kernel.hpp) repeats this arithmetic.
 // This header holds the kernel template only (also compiled by hipRTC for user problems given as row functions); the
 // launchers are in ocs_pipeline2_kernels.hip.  Registry problems use the shifted form of their rows (HAS_SHIFT), user
 // problems the generic g_row_f / g_row_q.

@@ -265,7 +265,9 @@ def test_known_answer_decoupled_linear_system(ocs, mapping, nS):
     recursion (RK4Integrator.m:37-51) has the closed form x_{i+1} = R(h lambda) x_i + h phi(h lambda) Bu u with the
     stability polynomial R(z) = 1 + z + z^2/2 + z^3/6 + z^4/24 and phi(z) = 1 + z/2 + z^2/6 + z^3/24; with the objective
     integrand e^{-rt} u'Ru alone the discrete adjoint (:72-88) is lam_i = R(h lambda) lam_{i+1} and dJ/du at the nodes follows
-    from the quadrature weights.  Checked in extended precision (numpy longdouble) on every LQ mapping."""
+    from the quadrature weights.  Checked in extended precision (numpy longdouble) on every LQ mapping.
+    The general form -- any A, time-varying u, q > 0, every node of every output -- is the extended-precision twin
+    tests/rk4_twin.py, against which tests/test_gpu_rk4_accuracy.py measures these kernels."""
     rng = np.random.default_rng(nS)
     nC, N, batch, T, r = 2, 48, 37, 1.2, 0.05
     lam_k = -rng.uniform(0.2, 6.0, nS)
