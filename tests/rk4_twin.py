@@ -31,7 +31,9 @@ WINDOW = 4           # nodes either side: one chunk of the lane and scan kernels
 
 
 def _ld(a):
-    return np.asarray(a, dtype=np.float64).astype(L)
+    """fp64 data as longdouble; an array that is longdouble already (the control between two sweeps of tests/fbs_twin.py) as it is"""
+    a = np.asarray(a)
+    return a if a.dtype == L else a.astype(np.float64).astype(L)
 
 
 def _per_traj(a, rows=None):

@@ -19,10 +19,9 @@ import pytest
 
 from tests import rk4_accuracy_cases as cs
 from tests import rk4_twin as tw
+from tests.accuracy_check import FLOOR, K, check_ratios   # noqa: F401  (K and the floor of the statement above)
 
 pytestmark = pytest.mark.gpu
-K = 8.0
-FLOOR = 8 * tw.EPS
 BOUNDS = [[0.0, 1.0]]
 
 
@@ -56,18 +55,7 @@ def _check(what, got, ref, err_oracle, sel, factor=None, subset=None):
     else:
         x = got["x"]
         e = {"x": tw.err(x[:-1], sub["x"]), "cost": tw.err(x[-1:], sub["cost"]), "J": tw.err_J(got["J"], sub["J"])}
-    ratios, bad = {}, []
-    for k, v in e.items():
-        yard_all = err_oracle[k][sel]
-        if subset and k in subset:
-            v, yard_all = v[subset[k]], yard_all[subset[k]]
-        yard = max(float(np.max(yard_all)), FLOOR)
-        ratios[k] = float(np.max(v)) / yard
-        if not np.all(v <= K * yard * (1.0 if factor is None else factor)):
-            bad.append((k, float(np.max(v)), yard))
-    print("ACCURACY", what, " ".join(f"{k}={r:.2f}" for k, r in ratios.items()) +
-          ("" if factor is None else f" (factor {np.min(factor):.0f}..{np.max(factor):.0f})"))
-    assert not bad, (what, "err_gpu > K * max(err_oracle, 8 eps) for (output, err_gpu, yardstick):", bad)
+    check_ratios(what, e, {k: err_oracle[k][sel] for k in e}, factor, subset)
 
 
 LOGISTIC = ([(m, nS) for nS in (1, 2, 4) for m in ("lane", "pipeline", "scan", "auto", "auto-whole")] +
