@@ -410,7 +410,9 @@ int ocs_fb_sweep_matrix_core(ocs_integrator g);
  * system by block elimination over time (one pivoted solve per interval and per node), step lengths 1, 1/2, 1/4, ...
  * accepted at ||Phi(y + a d)||_2 < (1 - 1e-4 a) ||Phi(y)||_2, stop at ||Phi||_inf <= NewtonTol.  An instance fails after
  * MaxIter iterations, after maxBacktracks halvings without an accepted step, or on a singular pivot / non-finite value; it
- * does not disturb the others.  bvp5c and its mesh adaptation are a MATLAB toolbox: results are those of the grid.
+ * does not disturb the others.  bvp5c is a MATLAB toolbox: one call solves on the grid it is given, and its results are
+ * those of that grid; ocs_bvp_rms and ocs_bvp_prolong below are the two device pieces of a mesh adaptation around it
+ * (the package's bvp_solver_adaptive_batch is that loop).
  * Custom bcFunc / yLJac / yRJac / optJac (:74-84, :115) are not supported.
  * Registry problems of the logistic family and plugin problems whose source defines ocs_ControlChar, nS <= 4, nC <= 2;
  * OCS_PROBLEM_LQ and larger plugins: OCS_ERR_UNSUPPORTED.
@@ -441,6 +443,34 @@ int ocs_bvp_solver_dev(ocs_integrator g, ocs_problem p, int batch, const double 
 int ocs_bvp_solver(ocs_integrator g, ocs_problem p, int batch, const double *x0, const ocs_bvp_options *opt,
                    const double *y0, const double *u0grid, double *ynodes, double *x, double *lam, double *uInterp,
                    double *J, int *iterations, int *converged, double *resnorm);
+
+/* ---- the mesh side of bvp_solver (bvpRelTol, MAX_MESH_SIZE of bvp_solver.m:15-19): how well does a nodal solution satisfy
+ * the differential equations between the nodes, and its values on another mesh ----
+ * With S the cubic Hermite interpolant through (y_i, f_i), (y_{i+1}, f_{i+1}), f = optSys at the nodes (ControlChar clamped,
+ * per-trajectory parameters and bounds as in ocs_bvp_solver), the residual r(t) = (S'(t) - optSys(t, S(t))) / (1 + |optSys(t,
+ * S(t))|), componentwise, is integrated over every interval by the five-point Lobatto rule (Kierzenka & Shampine's bvp4c; r
+ * vanishes at the nodes): rms_i = sqrt(1/2 (32/45 |r(t_m)|^2 + 49/90 (|r(t_+)|^2 + |r(t_-)|^2))), t_+- = t_m +- (h/2) sqrt(3/7),
+ * squared 2-norms over the 2 nS components -- estimate_rms_residuals of scipy.integrate.solve_bvp.
+ * device arrays, batch-minor: ynodes [N+1][2 nS][B]; use int [B] or NULL (= all); out: rms [N][B] or NULL (not wanted),
+ * rmsmax [N] = the largest rms of interval i over the instances with use[b] != 0 (0 if there is none), rmsinst [B] = the
+ * largest rms of instance b over the intervals, whatever use says.  A NaN counts as +inf in both maxima.  Maxima only: the
+ * same call gives the same bits.  Refuses what ocs_bvp_solver refuses.  Asynchronous on `stream`, except that the first call on
+ * an integrator uploads the Lobatto times of its grid with a blocking copy. */
+int ocs_bvp_rms_dev(ocs_integrator g, ocs_problem p, int batch, const double *ynodes, const int *use, double *rms,
+                    double *rmsmax, double *rmsinst, void *stream);
+/* host: ynodes 2nS x (N+1) x batch; use batch or NULL; rms N x batch or NULL; rmsmax N; rmsinst batch */
+int ocs_bvp_rms(ocs_integrator g, ocs_problem p, int batch, const double *ynodes, const int *use, double *rms,
+                double *rmsmax, double *rmsinst);
+/* S of ynodes_old (on the nodes of g_old) at nnew points: point j lies in interval idx[j] (0-based, 0 .. N-1) of g_old at
+ * theta[j] = (t - t_i) / h_i in [0, 1]; idx and theta are HOST arrays in both entry points.  theta 0 and 1 are the old
+ * nodes idx and idx + 1: their values are copied, bit for bit.  ynew: device [nnew][2 nS][B] -- with the nodes of a refined
+ * mesh as the points, the y0 of the next ocs_bvp_solver_dev.  Waits for `stream` before it uploads idx and theta and again
+ * before it returns: ynew is complete and idx, theta are the caller's again. */
+int ocs_bvp_prolong_dev(ocs_integrator g_old, ocs_problem p, int batch, const double *ynodes_old, int nnew, const int *idx,
+                        const double *theta, double *ynew, void *stream);
+/* host: ynodes_old 2nS x (N+1) x batch; ynew 2nS x nnew x batch */
+int ocs_bvp_prolong(ocs_integrator g_old, ocs_problem p, int batch, const double *ynodes_old, int nnew, const int *idx,
+                    const double *theta, double *ynew);
 
 /* ---- the batch axis over the GPUs of one node (the reference has no batch axis and no parallelism:
  * every entry point integrates one trajectory, tests/solve_test_problem.m:37) ----

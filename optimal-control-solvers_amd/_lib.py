@@ -104,6 +104,10 @@ _SIG = {
     "ocs_bvp_default_options": (C.c_int, [vp]),
     "ocs_bvp_solver": (C.c_int, [vp, vp, C.c_int, dp, vp, dp, dp, dp, dp, dp, dp, dp, ip, ip, dp]),
     "ocs_bvp_solver_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ocs_bvp_rms": (C.c_int, [vp, vp, C.c_int, dp, ip, dp, dp, dp]),
+    "ocs_bvp_rms_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ocs_bvp_prolong": (C.c_int, [vp, vp, C.c_int, dp, C.c_int, ip, dp, dp]),
+    "ocs_bvp_prolong_dev": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, ip, dp, vp, vp]),
     "ocs_multi_create": (C.c_int, [C.POINTER(vp), ip, C.c_int]),
     "ocs_multi_destroy": (C.c_int, [vp]),
     "ocs_multi_size": (C.c_int, [vp]),

@@ -25,6 +25,13 @@ struct ocs_bvp_state {
   DevBuf gx, gl;
   // host entry point
   DevBuf x0, y0, u0, y, xaug, lam, uint_, J, iters, conv, res, stage;
+  // the mesh side (ocs_bvp_rms, ocs_bvp_prolong): rms [N][B] where the caller wants none, its chunk maxima, the Lobatto
+  // points of the grid with their time coefficients (those follow the problem like TUI), the prolongation map
+  DevBuf rms, PM, TL, TCL, TUL, pidx, ptheta;
+  const ocs_problem_s* tl_prob = nullptr;
+  unsigned long long tl_version = 0;
+  // ... and their host entry points
+  DevBuf use, rmsmax, rmsinst, ynew;
 };
 void ocs_bvp_state_free(ocs_bvp_state* s) { delete s; }
 
@@ -42,6 +49,13 @@ static int bvp_refuse(const ocs_integrator_s* g, const ocs_problem_s* p, const o
   if (!(opt->NewtonTol > 0.0) || opt->MaxIter < 1 || opt->maxBacktracks < 0 || opt->maxBacktracks > 60 || opt->nINTERP_PTS < 2)
     return fail(OCS_ERR_INVALID, "bad options");
   return OCS_OK;
+}
+
+// the same refusals for the entry points that take no options (the mesh side)
+static int bvp_refuse(const ocs_integrator_s* g, const ocs_problem_s* p) {
+  ocs_bvp_options o;
+  ocs_bvp_default_options(&o);
+  return bvp_refuse(g, p, &o);
 }
 
 extern "C" {
@@ -235,6 +249,125 @@ int ocs_bvp_solver(ocs_integrator g, ocs_problem p, int batch, const double* x0,
   HIP_TRY(hipMemcpy(converged, f->conv.p, sizeof(int) * B, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(resnorm, f->res.p, sizeof(double) * B, hipMemcpyDeviceToHost));
   return st;
+}
+
+// ---- the mesh side: residual estimate of a nodal solution, prolongation to another mesh ----
+int ocs_bvp_rms_dev(ocs_integrator g, ocs_problem p, int batch, const double* ynodes, const int* use, double* rms,
+                    double* rmsmax, double* rmsinst, void* stream) {
+  OCS_TRY(refuse_tiled(g, "ocs_bvp_rms"));
+  OCS_TRACE("ocs_bvp_rms_dev");
+  if (!g || !p || !ynodes || !rmsmax || !rmsinst || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  OCS_TRY(bvp_refuse(g, p));
+  hipStream_t s = (hipStream_t)stream;
+  OCS_TRY(bind_problem(g, p, batch, s));
+  if (!g->bvp) g->bvp = new ocs_bvp_state();
+  ocs_bvp_state* f = g->bvp;
+  const int N = g->N;
+  const size_t B = (size_t)batch;
+  if (!f->TL.p) {   // t_m -/+ (h/2) sqrt(3/7) in fp64, like the grid itself: the same numbers for every implementation
+    std::vector<double> tl((size_t)2 * N);
+    const double s37 = std::sqrt(3.0 / 7.0);
+    for (int i = 0; i < N; ++i) {
+      const double d = g->h[i] / 2 * s37;
+      tl[2 * (size_t)i] = g->t[2 * (size_t)i + 1] - d;
+      tl[2 * (size_t)i + 1] = g->t[2 * (size_t)i + 1] + d;
+    }
+    OCS_TRY(f->TL.ensure(sizeof(double) * tl.size()));
+    HIP_TRY(hipMemcpy(f->TL.p, tl.data(), sizeof(double) * tl.size(), hipMemcpyHostToDevice));
+    f->tl_prob = nullptr;
+  }
+  const ProblemDesc pd = describe(p);
+  if (f->tl_prob != p || f->tl_version != p->version) {
+    OCS_TRY(f->TCL.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntc(p->functor, p->nS))));
+    OCS_TRY(f->TUL.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntu(p->functor, p->nS))));
+    LAUNCH_TRY(launch_tcoef_at(pd, 2 * N, f->TL.d(), f->TCL.d(), f->TUL.d(), s));
+    f->tl_prob = p;
+    f->tl_version = p->version;
+  }
+  if (!rms) {
+    OCS_TRY(f->rms.ensure(sizeof(double) * (size_t)N * B));
+    rms = f->rms.d();
+  }
+  OCS_TRY(f->PM.ensure(sizeof(double) * (size_t)bvp_chunks(N) * B));
+  LAUNCH_TRY(launch_bvp_rms(pd, describe(g), batch, f->TCL.d(), f->TUL.d(), ynodes, rms, f->PM.d(), s));
+  LAUNCH_TRY(launch_bvp_rms_reduce(N, batch, rms, f->PM.d(), use, rmsmax, rmsinst, s));
+  return OCS_OK;
+}
+
+int ocs_bvp_rms(ocs_integrator g, ocs_problem p, int batch, const double* ynodes, const int* use, double* rms,
+                double* rmsmax, double* rmsinst) {
+  OCS_TRACE("ocs_bvp_rms");
+  if (!g || !p || !ynodes || !rmsmax || !rmsinst || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  OCS_TRY(refuse_tiled(g, "ocs_bvp_rms"));
+  OCS_TRY(bvp_refuse(g, p));
+  OCS_TRY(upload_grid(g));
+  if (!g->bvp) g->bvp = new ocs_bvp_state();
+  ocs_bvp_state* f = g->bvp;
+  const int N = g->N, nY = 2 * p->nS;
+  const size_t B = (size_t)batch;
+  hipStream_t s = g->stream;
+  HIP_TRY(hipStreamSynchronize(s));   // (the stage buffer may still be in use)
+  OCS_TRY(stage_in(f->stage, f->y, ynodes, nY * (N + 1), batch, s));
+  if (use) {
+    OCS_TRY(f->use.ensure(sizeof(int) * B));
+    HIP_TRY(hipMemcpyAsync(f->use.p, use, sizeof(int) * B, hipMemcpyHostToDevice, s));
+  }
+  OCS_TRY(f->rms.ensure(sizeof(double) * (size_t)N * B));
+  OCS_TRY(f->rmsmax.ensure(sizeof(double) * (size_t)N));
+  OCS_TRY(f->rmsinst.ensure(sizeof(double) * B));
+  OCS_TRY(ocs_bvp_rms_dev(g, p, batch, f->y.d(), use ? (const int*)f->use.p : nullptr, f->rms.d(), f->rmsmax.d(),
+                          f->rmsinst.d(), s));
+  if (rms) OCS_TRY(stage_out(f->stage, f->rms.d(), rms, N, batch, s));
+  HIP_TRY(hipMemcpyAsync(rmsmax, f->rmsmax.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(rmsinst, f->rmsinst.p, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return OCS_OK;
+}
+
+int ocs_bvp_prolong_dev(ocs_integrator g_old, ocs_problem p, int batch, const double* ynodes_old, int nnew, const int* idx,
+                        const double* theta, double* ynew, void* stream) {
+  ocs_integrator g = g_old;
+  OCS_TRY(refuse_tiled(g, "ocs_bvp_prolong"));
+  OCS_TRACE("ocs_bvp_prolong_dev");
+  if (!g || !p || !ynodes_old || !idx || !theta || !ynew || batch < 1 || nnew < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  OCS_TRY(bvp_refuse(g, p));
+  if (nnew > 65535) return fail(OCS_ERR_UNSUPPORTED, "bvp_solver: %d steps are beyond its kernels (at most 65534)", nnew - 1);
+  for (int j = 0; j < nnew; ++j)
+    if (idx[j] < 0 || idx[j] >= g->N || !(theta[j] >= 0.0 && theta[j] <= 1.0))
+      return fail(OCS_ERR_INVALID, "ocs_bvp_prolong: node %d lies outside the old mesh (interval %d of %d, theta %g)", j, idx[j],
+                  g->N, theta[j]);
+  hipStream_t s = (hipStream_t)stream;
+  OCS_TRY(bind_problem(g, p, batch, s));
+  if (!g->bvp) g->bvp = new ocs_bvp_state();
+  ocs_bvp_state* f = g->bvp;
+  HIP_TRY(hipStreamSynchronize(s));   // (a map of an earlier call may still be read)
+  OCS_TRY(f->pidx.ensure(sizeof(int) * (size_t)nnew));
+  OCS_TRY(f->ptheta.ensure(sizeof(double) * (size_t)nnew));
+  HIP_TRY(hipMemcpyAsync(f->pidx.p, idx, sizeof(int) * (size_t)nnew, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(f->ptheta.p, theta, sizeof(double) * (size_t)nnew, hipMemcpyHostToDevice, s));
+  LAUNCH_TRY(launch_bvp_prolong(describe(p), describe(g), batch, ynodes_old, nnew, (const int*)f->pidx.p, f->ptheta.d(), ynew, s));
+  HIP_TRY(hipStreamSynchronize(s));   // (idx and theta are the caller's again)
+  return OCS_OK;
+}
+
+int ocs_bvp_prolong(ocs_integrator g_old, ocs_problem p, int batch, const double* ynodes_old, int nnew, const int* idx,
+                    const double* theta, double* ynew) {
+  ocs_integrator g = g_old;
+  OCS_TRACE("ocs_bvp_prolong");
+  if (!g || !p || !ynodes_old || !idx || !theta || !ynew || batch < 1 || nnew < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  OCS_TRY(refuse_tiled(g, "ocs_bvp_prolong"));
+  OCS_TRY(bvp_refuse(g, p));
+  OCS_TRY(upload_grid(g));
+  if (!g->bvp) g->bvp = new ocs_bvp_state();
+  ocs_bvp_state* f = g->bvp;
+  const int N = g->N, nY = 2 * p->nS;
+  hipStream_t s = g->stream;
+  HIP_TRY(hipStreamSynchronize(s));
+  OCS_TRY(stage_in(f->stage, f->y, ynodes_old, nY * (N + 1), batch, s));
+  OCS_TRY(f->ynew.ensure(sizeof(double) * (size_t)nnew * nY * batch));
+  OCS_TRY(ocs_bvp_prolong_dev(g, p, batch, f->y.d(), nnew, idx, theta, f->ynew.d(), s));
+  OCS_TRY(stage_out(f->stage, f->ynew.d(), ynew, nnew * nY, batch, s));
+  return OCS_OK;
 }
 
 }  // extern "C"

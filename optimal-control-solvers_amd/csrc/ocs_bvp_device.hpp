@@ -10,6 +10,11 @@
 //            as it stands
 // k_bvp_assemble turns every interval into the step map  dy_{i+1} = A_i dy_i + b_i  of the Newton system
 // (dPhi_i/dy_{i+1}) dy_{i+1} + (dPhi_i/dy_i) dy_i = -Phi_i;  k_bvp_norm evaluates Phi alone at a line-search trial point.
+//
+// The mesh side (bvp4c / solve_bvp's error control): with S the cubic Hermite interpolant of a nodal solution through
+// (y_i, f_i), (y_{i+1}, f_{i+1}), k_bvp_rms estimates the residual S' - optSys(t, S) of every interval by the five-point
+// Lobatto rule (zero at the nodes: the middle and t_m -/+ (h/2) sqrt(3/7) remain); k_bvp_prolong evaluates S at the nodes of
+// another mesh.
 #pragma once
 #include "ocs_device_common.hpp"
 
@@ -88,7 +93,8 @@ struct BvpRhs {
   typename P::Par p;
   double lb[NC], ub[NC];
   uniform_ptr TC, TU;
-  __device__ inline BvpRhs(const BvpArgs& a, int b)
+  template <class Args>   // (BvpArgs, BvpRmsArgs, BvpProlongArgs: the same member names)
+  __device__ inline BvpRhs(const Args& a, int b)
       : p(P::load(ParamSrc{as_uniform(a.ps), a.pb, a.pmask, (size_t)a.batch, b})), TC(as_uniform(a.TC)), TU(as_uniform(a.TU)) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -98,11 +104,15 @@ struct BvpRhs {
   }
   // f = optSys(t_j, y), j = grid point (2 i: node i, 2 i + 1: the middle of interval i)
   __device__ inline OCS_INLINE void operator()(int j, const double* y, double* f) const {
+    at(TC + (size_t)j * P::NTC, TU + (size_t)j * P::NTU, y, f);
+  }
+  // f = optSys(t, y) at a time with the coefficients tcp [NTC], tup [NTU] (a row of a table of its own: the Lobatto points)
+  __device__ inline OCS_INLINE void at(uniform_ptr tcp, uniform_ptr tup, const double* y, double* f) const {
     double tc[P::NTC], tu[P::NTU], u[NC], F[NS + 1], v[NS + 1], g[NS];
 #pragma unroll
-    for (int k = 0; k < P::NTC; ++k) tc[k] = TC[(size_t)j * P::NTC + k];
+    for (int k = 0; k < P::NTC; ++k) tc[k] = tcp[k];
 #pragma unroll
-    for (int k = 0; k < P::NTU; ++k) tu[k] = TU[(size_t)j * P::NTU + k];
+    for (int k = 0; k < P::NTU; ++k) tu[k] = tup[k];
     P::control_char(tu, y, y + NS, p, lb, ub, u);
     P::F(tc, y, u, p, F);
 #pragma unroll
@@ -263,6 +273,162 @@ __global__ __launch_bounds__(64) void k_bvp_norm(const BvpArgs a) {
   }
   a.SS[(size_t)blockIdx.y * B + b] = ss;
   a.MX[(size_t)blockIdx.y * B + b] = mx;
+}
+
+// ---------------------------------------------------------------------------------------
+// residual estimate of a nodal solution (estimate_rms_residuals of scipy's solve_bvp; Kierzenka & Shampine's bvp4c): per
+// interval and instance
+//   rms_i = sqrt( 1/2 ( 32/45 |r_m|^2 + 49/90 (|r_+|^2 + |r_-|^2) ) ),   r = (S' - optSys(t, S)) / (1 + |optSys(t, S)|)
+// componentwise, at t_m and t_m -/+ (h/2) sqrt(3/7).  With theta = (t - t_i) / h = 1/2 -/+ s, s = sqrt(3/7) / 2, and
+// theta (1 - theta) = 1/7 the Hermite weights are constants:
+//   S  = y_i + w (y_{i+1} - y_i) + h (a f_i - b f_{i+1}),   w = (9 theta - 1) / 7,  a = (1 - theta) / 7,  b = theta / 7
+//   S' = 6/7 (y_{i+1} - y_i) / h + (4/7 - theta) f_i + (theta - 3/7) f_{i+1}
+// The mapping of k_bvp_norm: one thread per (instance, chunk of kBvpChunk intervals), the right node's optSys kept as the
+// next left node's.  PM: the chunk's largest rms, a NaN counted as +inf.
+// ---------------------------------------------------------------------------------------
+struct BvpRmsArgs {
+  int N, batch;
+  const double* HT;
+  const double* TC;
+  const double* TU;
+  const double* TCL;   // [2N][NTC] time coefficients of the Lobatto points: 2 i at t_m - (h/2) sqrt(3/7), 2 i + 1 at t_m + ...
+  const double* TUL;   // [2N][NTU]
+  const double* ps;
+  const double* pb;
+  unsigned pmask;
+  const double* lb;
+  const double* ub;
+  int bstride;
+  const double* y;     // [N+1][2 nS][B]
+  double* rms;         // [N][B]
+  double* PM;          // [chunks][B]
+};
+
+constexpr double kLobS = 0.32732683535398857;   // sqrt(3/7) / 2
+
+template <class P>
+__global__ __launch_bounds__(64) void k_bvp_rms(const BvpRmsArgs a) {
+  constexpr int NY = 2 * P::NS;
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  const int i0 = blockIdx.y * kBvpChunk;
+  if (b >= a.batch || i0 >= a.N) return;
+  const size_t B = (size_t)a.batch;
+  const BvpRhs<P> rhs(a, b);
+  const uniform_ptr HT = as_uniform(a.HT), TCL = as_uniform(a.TCL), TUL = as_uniform(a.TUL);
+  double yl[NY], fl[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) yl[r] = a.y[((size_t)i0 * NY + r) * B + b];
+  rhs(2 * i0, yl, fl);
+  double pm = 0.0;
+  const int iend = i0 + kBvpChunk < a.N ? i0 + kBvpChunk : a.N;
+#pragma unroll 1
+  for (int i = i0; i < iend; ++i) {
+    const double h = HT[4 * (size_t)i], h8 = 0.125 * h;
+    double yr[NY], fr[NY], dy[NY], sl[NY], ys[NY], fs[NY];
+#pragma unroll
+    for (int r = 0; r < NY; ++r) yr[r] = a.y[((size_t)(i + 1) * NY + r) * B + b];
+    rhs(2 * i + 2, yr, fr);
+#pragma unroll
+    for (int r = 0; r < NY; ++r) {
+      dy[r] = yr[r] - yl[r];
+      sl[r] = dy[r] / h;
+    }
+    // |r|^2 of one point from S' there (sp) and optSys at S (fs)
+    auto norm2 = [&](const double* sp) OCS_INLINE {
+      double acc = 0.0;
+#pragma unroll
+      for (int r = 0; r < NY; ++r) {
+        const double q = (sp[r] - fs[r]) / (1.0 + fabs(fs[r]));
+        acc = __builtin_fma(q, q, acc);
+      }
+      return acc;
+    };
+    // the middle: S and S' are the collocation point and the collocation residual of the Simpson formula
+    double sp[NY];
+#pragma unroll
+    for (int r = 0; r < NY; ++r) {
+      ys[r] = __builtin_fma(h8, fl[r] - fr[r], 0.5 * (yl[r] + yr[r]));
+      sp[r] = 1.5 * sl[r] - 0.25 * (fl[r] + fr[r]);
+    }
+    rhs(2 * i + 1, ys, fs);
+    const double rm = norm2(sp);
+    double rpm = 0.0;
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+      const double th = side ? 0.5 + kLobS : 0.5 - kLobS;
+      const double w = (9.0 * th - 1.0) / 7.0, ca = (1.0 - th) / 7.0, cb = th / 7.0, da = 4.0 / 7.0 - th, db = th - 3.0 / 7.0;
+#pragma unroll
+      for (int r = 0; r < NY; ++r) {
+        ys[r] = yl[r] + w * dy[r] + h * (ca * fl[r] - cb * fr[r]);
+        sp[r] = (6.0 / 7.0) * sl[r] + da * fl[r] + db * fr[r];
+      }
+      rhs.at(TCL + (size_t)(2 * i + side) * P::NTC, TUL + (size_t)(2 * i + side) * P::NTU, ys, fs);
+      rpm += norm2(sp);
+    }
+    const double v = sqrt(0.5 * ((32.0 / 45.0) * rm + (49.0 / 90.0) * rpm));
+    a.rms[(size_t)i * B + b] = v;
+    pm = fmax(pm, v == v ? v : __builtin_inf());
+#pragma unroll
+    for (int r = 0; r < NY; ++r) {
+      yl[r] = yr[r];
+      fl[r] = fr[r];
+    }
+  }
+  a.PM[(size_t)blockIdx.y * B + b] = pm;
+}
+
+// ---------------------------------------------------------------------------------------
+// S of a nodal solution on the mesh of the integrator at the nodes of another mesh: new node j lies in interval idx[j] at
+// theta[j] = (t - t_i) / h in [0, 1].  theta == 0 and theta == 1 are the old nodes idx and idx + 1: copied, not evaluated
+// (the same bits).  One thread per (instance, new node); ynew [nnew][2 nS][B].
+// ---------------------------------------------------------------------------------------
+struct BvpProlongArgs {
+  int N, batch, nnew;
+  const double* HT;
+  const double* TC;
+  const double* TU;
+  const double* ps;
+  const double* pb;
+  unsigned pmask;
+  const double* lb;
+  const double* ub;
+  int bstride;
+  const double* y;       // [N+1][2 nS][B]
+  const int* idx;        // [nnew], 0 .. N-1
+  const double* theta;   // [nnew]
+  double* ynew;
+};
+
+template <class P>
+__global__ __launch_bounds__(64) void k_bvp_prolong(const BvpProlongArgs a) {
+  constexpr int NY = 2 * P::NS;
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y;
+  if (b >= a.batch || j >= a.nnew) return;
+  const size_t B = (size_t)a.batch;
+  const int i = a.idx[j];
+  const double th = a.theta[j];
+  if (i < 0 || i >= a.N) return;   // (the host has checked: nothing is read or written out of bounds whatever it passes)
+  double* dst = a.ynew + (size_t)j * NY * B + b;
+  if (th == 0.0 || th == 1.0) {
+    const double* src = a.y + (size_t)(th == 0.0 ? i : i + 1) * NY * B + b;
+#pragma unroll
+    for (int r = 0; r < NY; ++r) dst[(size_t)r * B] = src[(size_t)r * B];
+    return;
+  }
+  const BvpRhs<P> rhs(a, b);
+  double yl[NY], yr[NY], fl[NY], fr[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+    yl[r] = a.y[((size_t)i * NY + r) * B + b];
+    yr[r] = a.y[((size_t)(i + 1) * NY + r) * B + b];
+  }
+  rhs(2 * i, yl, fl);
+  rhs(2 * i + 2, yr, fr);
+  const double h = as_uniform(a.HT)[4 * (size_t)i];
+  const double w = th * th * (3.0 - 2.0 * th), ca = th * (1.0 - th) * (1.0 - th), cb = th * th * (1.0 - th);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) dst[(size_t)r * B] = yl[r] + w * (yr[r] - yl[r]) + h * (ca * fl[r] - cb * fr[r]);
 }
 
 }  // namespace ocs

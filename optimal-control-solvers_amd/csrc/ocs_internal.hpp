@@ -401,6 +401,18 @@ int launch_bvp_pack(int npts, int nS, int batch, const double* xs, int ldx, bool
                     hipStream_t s);
 int launch_bvp_costate_rows(int npts, int nS, int batch, const double* y, double* lam, hipStream_t s);
 int launch_bvp_converged(int batch, const int* status, int* converged, hipStream_t s);
+// the mesh side.  Residual estimate of a nodal solution y (k_bvp_rms, ocs_bvp_device.hpp): rms [N][B] and the chunk maxima
+// PM [bvp_chunks(N)][B]; TCL [2N][NTC], TUL [2N][NTU]: time coefficients of the Lobatto points (launch_tcoef_at)
+int launch_tcoef_at(const ProblemDesc& p, int nq, const double* tq, double* TCQ, double* TUQ, hipStream_t s);
+int launch_bvp_rms(const ProblemDesc& p, const GridDesc& g, int batch, const double* TCL, const double* TUL, const double* y,
+                   double* rms, double* PM, hipStream_t s);
+// rmsmax [N]: per interval the largest rms over the instances with use[b] != 0 (NULL: all); rmsinst [B]: per instance the
+// largest over the intervals; a NaN counts as +inf
+int launch_bvp_rms_reduce(int N, int batch, const double* rms, const double* PM, const int* use, double* rmsmax,
+                          double* rmsinst, hipStream_t s);
+// the Hermite interpolant of y on the grid of g at nnew points (interval idx, position theta in it): ynew [nnew][2 nS][B]
+int launch_bvp_prolong(const ProblemDesc& p, const GridDesc& g, int batch, const double* y, int nnew, const int* idx,
+                       const double* theta, double* ynew, hipStream_t s);
 
 // registry queries (host)
 bool functor_supported(Functor f, int nS, int nC);

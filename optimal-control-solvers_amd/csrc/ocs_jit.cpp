@@ -123,6 +123,8 @@ static std::vector<std::string> kernel_names(int nS, int nC, bool rowsep, bool f
   if (has_cc && vector_shape_ok(nS, nC)) {   // (bvp_solver refuses a plugin without ocs_ControlChar)
     n[UK_BVP_ASSEMBLE] = "ocs::k_bvp_assemble<ocs::UserP>";
     n[UK_BVP_NORM] = "ocs::k_bvp_norm<ocs::UserP>";
+    n[UK_BVP_RMS] = "ocs::k_bvp_rms<ocs::UserP>";
+    n[UK_BVP_PROLONG] = "ocs::k_bvp_prolong<ocs::UserP>";
   }
   return n;
 }

@@ -38,6 +38,8 @@ enum UserKernel : int {
   UK_CONTROL_PTS_SORTED,
   // nS <= 4, nC <= 2: assembly and residual of the batched bvp_solver (ocs_bvp_device.hpp)
   UK_BVP_ASSEMBLE, UK_BVP_NORM,
+  // ... and its mesh side: residual estimate of a nodal solution, prolongation to another mesh
+  UK_BVP_RMS, UK_BVP_PROLONG,
   UK_COUNT
 };
 

@@ -112,6 +112,19 @@ int launch_tcoef(const ProblemDesc& p, const GridDesc& g, hipStream_t s) {
   if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { run_tcoef<decltype(P)>(p, g, s); })) return -1;
   return hip_rc(hipGetLastError());
 }
+// the same two tables at nq times of the caller's (no step records): TCQ [nq][NTC], TUQ [nq][NTU]
+int launch_tcoef_at(const ProblemDesc& p, int nq, const double* tq, double* TCQ, double* TUQ, hipStream_t s) {
+  const dim3 grid((nq + 255) / 256), block(256);
+  if (p.functor == Functor::User) {
+    const double* ps = p.ps;
+    void* args[] = {&nq, &tq, &ps, &TCQ, &TUQ};
+    return jit_launch(p.user, UK_TCOEF, grid, block, args, s);
+  }
+  if (p.functor != Functor::Logistic) return -1;
+  if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { k_tcoef<decltype(P)><<<grid, block, 0, s>>>(nq, tq, p.ps, TCQ, TUQ); }))
+    return -1;
+  return hip_rc(hipGetLastError());
+}
 int rec_stride_host(int ntc) { return rec_stride(ntc); }
 int rec_sc_offset_host(int ntc) { return rec_sc_offset(ntc); }
 int rec_pad_host() { return kRecPad; }

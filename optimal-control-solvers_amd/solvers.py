@@ -438,3 +438,119 @@ def bvp_solver_batch(prob, x0, tspan, options=None, integrator=None):
                                       _p(uI), _p(J), iters.ctypes.data_as(ip), conv.ctypes.data_as(ip), _p(res)))
     return {"x": x, "lam": lam, "u": uI, "J": J, "y": y, "iterations": iters, "converged": conv.astype(bool),
             "resnorm": res, "status": status, "tspan": integ.tspan, "interpPts": interpPts}
+
+
+def bvp_residuals(prob, tspan, y, use=None, integrator=None):
+    """How well a nodal solution y (2nS x (N+1) [x batch], on the nodes of tspan) satisfies y' = optSys(t, y) between the
+    nodes (ocs_bvp_rms): the rms residual of its cubic Hermite interpolant per interval, (S' - optSys) / (1 + |optSys|) under
+    the five-point Lobatto rule -- estimate_rms_residuals of scipy.integrate.solve_bvp, bvp4c's error estimate.
+    use: batch flags, the instances that count in rmsmax (default all).  Returns {"rms": N x batch, "rmsmax": N (largest
+    over the instances in use), "rmsinst": batch (largest over the intervals)}; a NaN counts as inf in both maxima."""
+    from ._lib import ip
+    integ = integrator or RK4Integrator(tspan)
+    N, nS = integ.nSTEPS, prob.nS
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim == 2:
+        y = y[:, :, None]
+    batch = y.shape[2]
+    y = _f(y, (2 * nS, N + 1, batch))
+    usep = None
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use).ravel() != 0, dtype=np.int32)
+        if use.size != batch:
+            raise ValueError(f"use: expected {batch} flags, got {use.size}")
+        usep = use.ctypes.data_as(ip)
+    rms = np.empty((N, batch), order="F")
+    rmsmax, rmsinst = np.empty(N), np.empty(batch)
+    check(lib.ocs_bvp_rms(integ._h, prob._h, batch, _p(y), usep, _p(rms), _p(rmsmax), _p(rmsinst)))
+    return {"rms": rms, "rmsmax": rmsmax, "rmsinst": rmsinst}
+
+
+def _refine_mesh(mesh, rmsmax, tol):
+    """modify_mesh of scipy.integrate.solve_bvp with its rule for what to insert: one node in the middle of the intervals
+    with tol < rmsmax < 100 tol, two nodes at the thirds of those with rmsmax >= 100 tol (a NaN counts as such).  Returns
+    the new mesh; nodes are only added."""
+    mesh, r = np.asarray(mesh, dtype=np.float64), np.asarray(rmsmax, dtype=np.float64)
+    r = np.where(np.isnan(r), np.inf, r)
+    i1, = np.nonzero((r > tol) & (r < 100 * tol))
+    i2, = np.nonzero(r >= 100 * tol)
+    return np.sort(np.hstack((mesh, 0.5 * (mesh[i1] + mesh[i1 + 1]), (2 * mesh[i2] + mesh[i2 + 1]) / 3,
+                              (mesh[i2] + 2 * mesh[i2 + 1]) / 3)))
+
+
+def _prolong_map(old, new):
+    """Where the nodes of `new` lie on the mesh `old`: (idx int32, theta) with new = old[idx] + theta (old[idx + 1] - old[idx]),
+    0 <= theta <= 1; a node of `old` has theta 0 (the last one: theta 1 in the last interval)."""
+    old, new = np.asarray(old, dtype=np.float64), np.asarray(new, dtype=np.float64)
+    idx = np.clip(np.searchsorted(old, new, side="right") - 1, 0, old.size - 2)
+    theta = (new - old[idx]) / (old[idx + 1] - old[idx])
+    return np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(theta)
+
+
+def bvp_prolong(prob, tspan, y, new_tspan, integrator=None):
+    """The cubic Hermite interpolant of a nodal solution y (2nS x (N+1) x batch on tspan; slopes optSys at the nodes) at the
+    nodes of new_tspan (ocs_bvp_prolong): 2nS x len(new_tspan) x batch.  Nodes of tspan are copied, not evaluated."""
+    from ._lib import ip
+    integ = integrator or RK4Integrator(tspan)
+    N, nS = integ.nSTEPS, prob.nS
+    y = np.asarray(y, dtype=np.float64)
+    batch = y.shape[2]
+    y = _f(y, (2 * nS, N + 1, batch))
+    idx, theta = _prolong_map(integ.tspan, new_tspan)
+    out = np.empty((2 * nS, idx.size, batch), order="F")
+    check(lib.ocs_bvp_prolong(integ._h, prob._h, batch, _p(y), idx.size, idx.ctypes.data_as(ip), _p(theta), _p(out)))
+    return out
+
+
+def bvp_solver_adaptive_batch(prob, x0, tspan, options=None):
+    """bvp_solver_batch with the mesh adaptation that bvp_solver.m:15-19,112 asks of bvp5c, as scipy.integrate.solve_bvp does
+    it: solve on a mesh, estimate the residual of the solution between the nodes (bvp_residuals), add nodes where it exceeds
+    the tolerance, start again from the interpolant (bvp_prolong) -- until the estimate is below the tolerance on every
+    interval.  The batch shares the mesh: it is refined wherever any Newton-converged instance needs it.
+    options: everything bvp_solver_batch takes, and
+      InitMesh       the first mesh, default linspace(T0, TF, 11) (bvp_solver.m:22); tspan only gives T0 and TF
+      bvpRelTol      the bound on the rms residual (scipy's tol), default 1e-6; bvpAbsTol is ignored with a warning (the
+                     estimate is normalised by 1 + |optSys|, there is no second knob)
+      MAX_MESH_SIZE  nodes, default 1000: a refinement that would go beyond it is not made
+      y0 / u0        belong to the first mesh: a callable is sampled there, arrays must match InitMesh
+    Returns the dict of bvp_solver_batch on the last mesh, and: mesh (= tspan), rms (N x batch), rms_ok (per instance:
+    converged and its own largest rms <= tol), meshes (the node count of every round), mesh_status -- 0: the tolerance
+    holds on every interval; 1: the next mesh would exceed MAX_MESH_SIZE; 2: no instance converged on a mesh."""
+    from .sweep import matlab_linspace
+    options = dict(options or {})
+    tspan = _f(tspan).ravel()
+    tol = float(options.pop("bvpRelTol", 1e-6))
+    max_nodes = int(options.pop("MAX_MESH_SIZE", 1000))
+    if "bvpAbsTol" in options:
+        import warnings
+        options.pop("bvpAbsTol")
+        warnings.warn("bvp_solver_adaptive_batch: bvpAbsTol has no effect (the residual estimate is normalised by 1 + |optSys|; "
+                      "bvpRelTol is its one tolerance)", RuntimeWarning, stacklevel=2)
+    mesh = options.pop("InitMesh", None)
+    mesh = matlab_linspace(tspan[0], tspan[-1], 11) if mesh is None else _f(mesh).ravel().copy()
+    if not tol > 0 or mesh.size < 2 or np.any(np.diff(mesh) <= 0):
+        raise ValueError("bvp_solver_adaptive_batch: need bvpRelTol > 0 and an increasing InitMesh")
+    meshes = []
+    while True:
+        integ = RK4Integrator(mesh)
+        res = bvp_solver_batch(prob, x0, mesh, options, integrator=integ)
+        meshes.append(int(mesh.size))
+        est = bvp_residuals(prob, mesh, res["y"], use=res["converged"], integrator=integ)
+        if not res["converged"].any():
+            status = 2
+            break
+        new = _refine_mesh(mesh, est["rmsmax"], tol)
+        if new.size == mesh.size:
+            status = 0
+            break
+        if new.size > max_nodes:
+            status = 1
+            break
+        start = bvp_prolong(prob, mesh, res["y"], new, integrator=integ)
+        del integ                                    # (the handle's bvp workspace goes with it)
+        options.pop("u0", None)
+        options["y0"] = start
+        mesh = new
+    res.update(mesh=res["tspan"], rms=est["rms"], rms_ok=res["converged"] & (est["rmsinst"] <= tol), mesh_status=status,
+               meshes=meshes)
+    return res
