@@ -550,11 +550,12 @@ def test_fused_banded_control_objective_gradient(ocs, oracle, kind, nS, nB, N, b
     x0 = rng.uniform(0.8, 1.5, (nS, batch))
     pg = ocs.LogisticProblem(m, P["c"], P["r"], BOUNDS)
     pg.set_batch_params([0], cs[None, :])
+    # "on", not "lane": the banded kernels are selected by fusion mode "on" alone below batch 32768 (ocs_nlp_objective_dev)
     out = {}
-    for mode in ("lane", "off"):
+    for mode in ("on", "off"):
         cg.set_fusion(mode)
         out[mode] = ocs.nlp_objective(g, pg, cg, x0.copy(), V, FreeInitStates=free)
-    Jf, df, x0f = out["lane"]
+    Jf, df, x0f = out["on"]
     Ju, du, x0u = out["off"]
     assert relerr(Jf, Ju) < 1e-13 and relerr(df, du) < RTOL and np.array_equal(x0f, x0u)
     for b in sorted({0, batch // 2, batch - 1}):

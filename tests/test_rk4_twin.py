@@ -72,7 +72,8 @@ def _mp_passes(fns, tspan, x0, u, lamT):
     tg, hg = tw.grid(tspan)
     t, h = _mpf(tg), _mpf(hg)
     N, nA, nC = len(h), len(x0) + 1, u.shape[0]
-    uc = [[mp.mpf(float(u[c, j])) for c in range(nC)] for j in range(2 * N + 1)]
+    # (u: fp64 samples, or mpf samples as they are -- tests/test_nlp_twin.py hands over a control that is not fp64 data)
+    uc = [[u[c, j] if isinstance(u[c, j], mp.mpf) else mp.mpf(float(u[c, j])) for c in range(nC)] for j in range(2 * N + 1)]
     axpy = lambda y, a, f: [y[k] + a * f[k] for k in range(nA)]
     xK = [[None] * 4 for _ in range(N + 1)]
     xK[0][0] = _mpf(x0) + [mp.mpf(0)]
