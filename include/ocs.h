@@ -402,6 +402,40 @@ int ocs_fb_sweep_path(ocs_integrator g);
  * sweep loops are the same, only the two passes inside them differ. */
 int ocs_fb_sweep_matrix_core(ocs_integrator g);
 
+/* ---- what RelTol / AbsTol of fb_sweep.m:18-19, compute_x_lam.m:8,12 steer in the reference: the error of the two passes ----
+ * x and lam of ocs_compute_x_lam under ugrid are fixed-step RK4 on the grid; this estimates, per interval i and instance,
+ * their local error against the continuous problem under that control by step doubling.  The control between its 2N+1
+ * samples is their pchip interpolant on the grid t, evaluated at t_i + h/4 and t_i + 3h/4.
+ *   state    from [x_i; 0] one RK4 step of h (the pass's) and two of h/2:  ex = 16/15 |fine - coarse| per state row, and
+ *            dJ_i = 16/15 ((coarse - fine) of the running-objective row + lam_{i+1}' (coarse - fine) of the state rows),
+ *            signed: the step's share of J(grid) - J(continuous) to first order -- its own cost error and what its state
+ *            error does to the objective of the rest of the horizon, whose derivative by the state lam is
+ *   costate  from lam_{i+1} backward one RK4 step of h as the pass does it (x at the nodes and at the pchip midpoint of the
+ *            node values) and two of h/2 whose states are x_{i+1}, the fine state x^_m after its first half step, x_i and,
+ *            at the quarter points, the cubic Hermite interpolant through (x_i, f_i), (x^_m, f^_m), (x_{i+1}, f_{i+1}), f
+ *            the state right-hand side there:  el = 16/15 |fine - coarse| per row.  The fine steps do not use the pchip
+ *            of the nodes, so el contains the coupling error of the pass.
+ *   ratios   rx_i = max_k ex_k / (AbsTol + RelTol max(|x_{i,k}|, |x_{i+1,k}|)),  rl_i the same with el and lam
+ * device arrays, batch-minor: ugrid [2N+1][nC][B]; x [N+1][ldx][B] with ldx = nS, or nS + 1 for the xaug of
+ * ocs_compute_x_lam_dev (its last row is not read); lam [N+1][nS][B]; use int [B] or NULL (= all).  Out: rx, rl [N][B], either
+ * may be NULL (not wanted); rmax [N] = the larger ratio of interval i over the instances with use[b] != 0 (0 if there is
+ * none); rinst [B] = the largest ratio of instance b over the intervals, whatever use says; errJ [B] = sum_i dJ_i, the estimated error of J, summed
+ * per chunk of 8 intervals and then over the chunks, in order.  A NaN counts as +inf in both maxima.  No floating-point
+ * atomics: the same call gives the same bits.  Only F and dFdx_times_vec are evaluated, ControlChar never; per-trajectory
+ * parameters apply as in ocs_compute_x_lam.
+ * Registry problems of the logistic family and plugin problems with nS <= 4, nC <= 2.  OCS_ERR_UNSUPPORTED: OCS_PROBLEM_LQ,
+ * larger plugins, an RK4InfiniteIntegrator handle, a handle set to the tiled layout.  OCS_ERR_INVALID: RelTol < 0, AbsTol < 0
+ * or both zero.  Asynchronous on `stream`, except that the first call on an integrator uploads the tables of the quarter
+ * points with blocking copies. */
+int ocs_x_lam_err_dev(ocs_integrator g, ocs_problem p, int batch, const double *ugrid, const double *x, int ldx,
+                      const double *lam, double RelTol, double AbsTol, const int *use, double *rx, double *rl, double *rmax,
+                      double *rinst, double *errJ, void *stream);
+/* host: ugrid nC x (2N+1) x batch; x, lam nS x (N+1) x batch; use batch or NULL; rx, rl N x batch or NULL; rmax N; rinst,
+ * errJ batch */
+int ocs_x_lam_err(ocs_integrator g, ocs_problem p, int batch, const double *ugrid, const double *x, const double *lam,
+                  double RelTol, double AbsTol, const int *use, double *rx, double *rl, double *rmax, double *rinst,
+                  double *errJ);
+
 /* ---- soln = bvp_solver(prob, x0, tspan, options)   functions/bvp_solver.m:1-134 for a batch of instances ----
  * The optimality system y' = optSys(t, y), y = [x; lam] (:105-109, through the same Gen-2 -> Gen-1 adapter as fb_sweep,
  * ControlChar clamped to each trajectory's own bounds where they are set), with x(T0) = x0, lam(TF) = 0 (:66), is

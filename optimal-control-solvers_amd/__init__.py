@@ -21,7 +21,8 @@ from .interp import vectorInterpolant, vectorInterpolant_dev, heval, linspace  #
 from .solvers import (nlp_objective, nlp_objective_dev, single_shooting, single_shooting_batch,  # noqa: F401
                       compute_equilibrium, compute_equilibrium_dev, bvp_solver_batch, bvp_residuals, bvp_prolong,
                       bvp_solver_adaptive_batch)
-from .sweep import fb_sweep, fb_sweep_batch, fb_sweep_dev, fb_sweep_path, fb_sweep_matrix_core, compute_x_lam, compute_x_lam_J, compute_J  # noqa: F401
+from .sweep import (fb_sweep, fb_sweep_batch, fb_sweep_dev, fb_sweep_path, fb_sweep_matrix_core, compute_x_lam,  # noqa: F401
+                    compute_x_lam_J, compute_J, x_lam_error, fb_sweep_adaptive_batch)
 from . import distributed  # noqa: F401
 from .multi import MultiDevice  # noqa: F401
 

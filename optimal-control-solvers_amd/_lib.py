@@ -99,6 +99,8 @@ _SIG = {
     "ocs_single_shooting_batch_bounds_dev": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, ip, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ocs_compute_x_lam": (C.c_int, [vp, vp, C.c_int, dp, dp, dp, dp, dp]),
     "ocs_compute_x_lam_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ocs_x_lam_err": (C.c_int, [vp, vp, C.c_int, dp, dp, dp, C.c_double, C.c_double, ip, dp, dp, dp, dp, dp]),
+    "ocs_x_lam_err_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
     "ocs_fb_sweep": (C.c_int, [vp, vp, C.c_int, dp, vp, dp, dp, dp, dp, dp, dp, ip, dp]),
     "ocs_fb_sweep_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ocs_bvp_default_options": (C.c_int, [vp]),

@@ -42,6 +42,14 @@ struct ocs_fbs_state {
   DevBuf nact_slots;                // device: the same counters
   // work arrays
   DevBuf xaug, xmid, lam, lmid, ugrid, uerr, uint_, J, usel, status, maxchange, nactive, x0, stage, metric, anyvalid, dump;
+  // the error estimate (ocs_x_lam_err): pchip tables of the grid t (spacings, slope weights), the quarter points (local
+  // coordinates, times; their time coefficients follow the problem like TUI), ratios where the caller wants none, chunk
+  // partials -- and the arrays of its host entry point
+  DevBuf eHG, eW1G, eW2G, eSQ, eTQ, eTCQ, eTUQ, erx, erl, ePM, ePJ;
+  bool etables = false;
+  const ocs_problem_s* etc_prob = nullptr;
+  unsigned long long etc_version = 0;
+  DevBuf eu, ex, elam, euse, ermax, erinst, eerrJ;
   ~ocs_fbs_state() {
     if (lq_event) (void)hipEventDestroy(lq_event);
     for (hipEvent_t e : wevents) (void)hipEventDestroy(e);
@@ -800,6 +808,117 @@ int ocs_compute_x_lam(ocs_integrator g, ocs_problem p, int batch, const double* 
   OCS_TRY(stage_out_states(f->stage, f->xaug.d(), x, nS, N + 1, batch, s));
   OCS_TRY(stage_out(f->stage, f->lam.d(), lam, (N + 1) * nS, batch, s));
   if (J) HIP_TRY(hipMemcpy(J, f->J.p, sizeof(double) * B, hipMemcpyDeviceToHost));
+  return OCS_OK;
+}
+
+// ---- how far are x and lam of compute_x_lam from the continuous problem under ugrid: step doubling per interval ----
+static int xlam_err_refuse(const ocs_integrator_s* g, const ocs_problem_s* p, double rtol, double atol) {
+  OCS_TRY(refuse_tiled(g, "ocs_x_lam_err"));
+  if (!(rtol >= 0.0) || !(atol >= 0.0) || (rtol == 0.0 && atol == 0.0))
+    return fail(OCS_ERR_INVALID, "ocs_x_lam_err: need RelTol >= 0, AbsTol >= 0 and one of them positive (got %g, %g)", rtol, atol);
+  if (g->kind != 0) return fail(OCS_ERR_UNSUPPORTED, "ocs_x_lam_err needs an RK4Integrator grid");
+  if (p->functor == Functor::LQ)
+    return fail(OCS_ERR_UNSUPPORTED, "ocs_x_lam_err: OCS_PROBLEM_LQ is not supported (logistic family and plugins with nS <= 4, nC <= 2)");
+  if (!xlam_err_supported(describe(p)))
+    return fail(OCS_ERR_UNSUPPORTED, "ocs_x_lam_err: nS = %d, nC = %d is beyond its kernel (nS <= 4, nC <= 2)", p->nS, p->nC);
+  return OCS_OK;
+}
+
+int ocs_x_lam_err_dev(ocs_integrator g, ocs_problem p, int batch, const double* ugrid, const double* x, int ldx,
+                      const double* lam, double RelTol, double AbsTol, const int* use, double* rx, double* rl, double* rmax,
+                      double* rinst, double* errJ, void* stream) {
+  OCS_TRACE("ocs_x_lam_err_dev");
+  if (!g || !p || !ugrid || !x || !lam || !rmax || !rinst || !errJ || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  if (ldx != p->nS && ldx != p->nS + 1) return fail(OCS_ERR_INVALID, "ocs_x_lam_err: ldx must be nS or nS + 1 (got %d)", ldx);
+  OCS_TRY(xlam_err_refuse(g, p, RelTol, AbsTol));
+  hipStream_t s = (hipStream_t)stream;
+  OCS_TRY(bind_problem(g, p, batch, s));
+  OCS_TRY(ensure_tables(g));
+  ocs_fbs_state* f = g->fbs;
+  const int N = g->N, nG = 2 * N + 1;
+  const size_t B = (size_t)batch;
+  if (!f->etables) {   // everything in fp64 from the grid, like the grid itself: the same numbers for every implementation
+    std::vector<double> hg((size_t)nG - 1), w1(nG), w2(nG), tq((size_t)2 * N), sq((size_t)2 * N);
+    for (int j = 0; j + 1 < nG; ++j) hg[j] = g->t[(size_t)j + 1] - g->t[j];
+    pchip_weights(nG, hg.data(), w1.data(), w2.data());
+    for (int i = 0; i < N; ++i) {
+      tq[2 * (size_t)i] = g->t[2 * (size_t)i] + 0.25 * g->h[i];
+      tq[2 * (size_t)i + 1] = g->t[2 * (size_t)i] + 0.75 * g->h[i];
+      sq[2 * (size_t)i] = tq[2 * (size_t)i] - g->t[2 * (size_t)i];
+      sq[2 * (size_t)i + 1] = tq[2 * (size_t)i + 1] - g->t[2 * (size_t)i + 1];
+    }
+    OCS_TRY(upload(f->eHG, hg.data(), sizeof(double) * hg.size()));
+    OCS_TRY(upload(f->eW1G, w1.data(), sizeof(double) * w1.size()));
+    OCS_TRY(upload(f->eW2G, w2.data(), sizeof(double) * w2.size()));
+    OCS_TRY(upload(f->eTQ, tq.data(), sizeof(double) * tq.size()));
+    OCS_TRY(upload(f->eSQ, sq.data(), sizeof(double) * sq.size()));
+    f->etables = true;
+    f->etc_prob = nullptr;
+  }
+  const ProblemDesc pd = describe(p);
+  if (f->etc_prob != p || f->etc_version != p->version) {
+    OCS_TRY(f->eTCQ.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntc(p->functor, p->nS))));
+    OCS_TRY(f->eTUQ.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntu(p->functor, p->nS))));
+    LAUNCH_TRY(launch_tcoef_at(pd, 2 * N, f->eTQ.d(), f->eTCQ.d(), f->eTUQ.d(), s));
+    f->etc_prob = p;
+    f->etc_version = p->version;
+  }
+  if (!rx) {
+    OCS_TRY(f->erx.ensure(sizeof(double) * (size_t)N * B));
+    rx = f->erx.d();
+  }
+  if (!rl) {
+    OCS_TRY(f->erl.ensure(sizeof(double) * (size_t)N * B));
+    rl = f->erl.d();
+  }
+  const size_t parts = (size_t)xlam_err_chunks(N);
+  OCS_TRY(f->ePM.ensure(sizeof(double) * parts * B));
+  OCS_TRY(f->ePJ.ensure(sizeof(double) * parts * B));
+  const XlamErrTables tq{f->eHG.d(), f->eW1G.d(), f->eW2G.d(), f->eSQ.d(), f->eTCQ.d()};
+  LAUNCH_TRY(launch_xlam_err(pd, describe(g), tabs(g), tq, batch, ugrid, x, ldx, lam, RelTol, AbsTol, rx, rl, f->ePM.d(),
+                             f->ePJ.d(), s));
+  LAUNCH_TRY(launch_xlam_err_reduce(N, batch, rx, rl, f->ePM.d(), f->ePJ.d(), use, rmax, rinst, errJ, s));
+  return OCS_OK;
+}
+
+// host: ugrid nC x (2N+1) x batch, x and lam nS x (N+1) x batch; use batch or NULL; rx, rl N x batch or NULL; rmax N; rinst,
+// errJ batch
+int ocs_x_lam_err(ocs_integrator g, ocs_problem p, int batch, const double* ugrid, const double* x, const double* lam,
+                  double RelTol, double AbsTol, const int* use, double* rx, double* rl, double* rmax, double* rinst,
+                  double* errJ) {
+  OCS_TRACE("ocs_x_lam_err");
+  if (!g || !p || !ugrid || !x || !lam || !rmax || !rinst || !errJ || batch < 1) return fail(OCS_ERR_INVALID, "bad argument");
+  OCS_TRY(xlam_err_refuse(g, p, RelTol, AbsTol));
+  OCS_TRY(upload_grid(g));
+  OCS_TRY(ensure_tables(g));
+  ocs_fbs_state* f = g->fbs;
+  const int N = g->N, nS = p->nS, nC = p->nC;
+  const size_t B = (size_t)batch;
+  hipStream_t s = g->stream;
+  HIP_TRY(hipStreamSynchronize(s));   // (before every stage_in here: the stage buffer may still be in use)
+  OCS_TRY(stage_in(f->stage, f->eu, ugrid, nC * (2 * N + 1), batch, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  OCS_TRY(stage_in(f->stage, f->ex, x, nS * (N + 1), batch, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  OCS_TRY(stage_in(f->stage, f->elam, lam, nS * (N + 1), batch, s));
+  if (use) {
+    OCS_TRY(f->euse.ensure(sizeof(int) * B));
+    HIP_TRY(hipMemcpyAsync(f->euse.p, use, sizeof(int) * B, hipMemcpyHostToDevice, s));
+  }
+  OCS_TRY(f->erx.ensure(sizeof(double) * (size_t)N * B));
+  OCS_TRY(f->erl.ensure(sizeof(double) * (size_t)N * B));
+  OCS_TRY(f->ermax.ensure(sizeof(double) * (size_t)N));
+  OCS_TRY(f->erinst.ensure(sizeof(double) * B));
+  OCS_TRY(f->eerrJ.ensure(sizeof(double) * B));
+  OCS_TRY(ocs_x_lam_err_dev(g, p, batch, f->eu.d(), f->ex.d(), nS, f->elam.d(), RelTol, AbsTol,
+                            use ? (const int*)f->euse.p : nullptr, f->erx.d(), f->erl.d(), f->ermax.d(), f->erinst.d(),
+                            f->eerrJ.d(), s));
+  if (rx) OCS_TRY(stage_out(f->stage, f->erx.d(), rx, N, batch, s));
+  if (rl) OCS_TRY(stage_out(f->stage, f->erl.d(), rl, N, batch, s));
+  HIP_TRY(hipMemcpyAsync(rmax, f->ermax.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(rinst, f->erinst.p, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(errJ, f->eerrJ.p, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return OCS_OK;
 }
 

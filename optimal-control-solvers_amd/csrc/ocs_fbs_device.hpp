@@ -9,61 +9,7 @@
 #endif
 namespace ocs {
 
-// ---------------------------------------------------------------------------------------
-// pchip (Fritsch-Carlson slopes as in MATLAB pchip / Moler's pchiptx), per lane
-// ---------------------------------------------------------------------------------------
-__device__ static inline int dsgn(double v) { return (v > 0.0) - (v < 0.0); }
-
-// interior node: weighted harmonic mean of the neighbouring secants, 0 at a local extremum
-__device__ static inline double pchip_interior(double del0, double del1, double w1, double w2) {
-  if (dsgn(del0) * dsgn(del1) <= 0) return 0.0;
-  const double a0 = fabs(del0), a1 = fabs(del1);
-  const double dmax = fmax(a0, a1), dmin = fmin(a0, a1);
-  return dmin / (w1 * (del0 / dmax) + w2 * (del1 / dmax));
-}
-// end node: non-centred three-point formula with the two shape-preserving corrections
-__device__ static inline double pchip_end(double h0, double h1, double del0, double del1) {
-  double d = ((2.0 * h0 + h1) * del0 - h0 * del1) / (h0 + h1);
-  if (dsgn(d) != dsgn(del0))
-    d = 0.0;
-  else if (dsgn(del0) != dsgn(del1) && fabs(d) > fabs(3.0 * del0))
-    d = 3.0 * del0;
-  return d;
-}
-
-// Node tables (uniform): TN[0..n-1] node times, HN[0..n-2] spacings, W1/W2[1..n-2] slope weights, IH = 1./HN.
-struct PchipTab {
-  int n;
-  const double* TN;
-  const double* HN;
-  const double* W1;
-  const double* W2;
-  const double* IH;  // 1 ./ HN
-};
-
-// slope at node k of the samples v(k) = V[(k*ld + row)*B + b]
-__device__ static inline double pchip_slope_at(const PchipTab& T, const double* V, size_t ldB, int k) {
-  const int n = T.n;
-  auto val = [&](int j) OCS_INLINE { return V[(size_t)j * ldB]; };
-  if (n == 2) return (val(1) - val(0)) / T.HN[0];
-  if (k == 0) {
-    const double d0 = (val(1) - val(0)) / T.HN[0], d1 = (val(2) - val(1)) / T.HN[1];
-    return pchip_end(T.HN[0], T.HN[1], d0, d1);
-  }
-  if (k == n - 1) {
-    const double d0 = (val(n - 1) - val(n - 2)) / T.HN[n - 2], d1 = (val(n - 2) - val(n - 3)) / T.HN[n - 3];
-    return pchip_end(T.HN[n - 2], T.HN[n - 3], d0, d1);
-  }
-  const double d0 = (val(k) - val(k - 1)) / T.HN[k - 1], d1 = (val(k + 1) - val(k)) / T.HN[k];
-  return pchip_interior(d0, d1, T.W1[k], T.W2[k]);
-}
-// cubic Hermite piece on an interval of length h with end values v0, v1 and end slopes dk, dk1 (pwch + ppval)
-__device__ static inline double pchip_piece(double v0, double v1, double dk, double dk1, double h, double s) {
-  const double del = (v1 - v0) / h;
-  const double dzzdx = (del - dk) / h, dzdxdx = (dk1 - del) / h;
-  const double c3 = (dzdxdx - dzzdx) / h, c2 = 2.0 * dzzdx - dzdxdx;
-  return v0 + s * (dk + s * (c2 + s * c3));
-}
+// (pchip per lane -- PchipTab, pchip_slope_at, pchip_piece -- is in ocs_device_common.hpp: ocs_xlam_err_device.hpp uses it too)
 // interpolant in interval k at local coordinate s = q - TN[k]
 __device__ static inline double pchip_eval(const PchipTab& T, const double* V, size_t ldB, int k, double s) {
   const double v0 = V[(size_t)k * ldB], v1 = V[(size_t)(k + 1) * ldB];

@@ -414,6 +414,26 @@ int launch_bvp_rms_reduce(int N, int batch, const double* rms, const double* PM,
 int launch_bvp_prolong(const ProblemDesc& p, const GridDesc& g, int batch, const double* y, int nnew, const int* idx,
                        const double* theta, double* ynew, hipStream_t s);
 
+// error estimate of the sweep's pass pair by step doubling (ocs_xlam_err_kernels.hip, k_xlam_err in ocs_xlam_err_device.hpp)
+struct XlamErrTables {   // device; what the estimate needs beside the integrator's and the sweep's tables
+  const double* HG;      // [2N] spacings of the grid t (nodes and middles): pchip of the control samples
+  const double* W1G;     // [2N+1] its interior slope weights (entries 1 .. 2N-1 used)
+  const double* W2G;
+  const double* SQ;      // [2N] local coordinates of the quarter points t_i + h/4, t_i + 3h/4 in their grid intervals
+  const double* TCQ;     // [2N][NTC] F-side time coefficients of the quarter points (launch_tcoef_at)
+};
+bool xlam_err_supported(const ProblemDesc& p);   // registry logistic family and user problems, nS <= 4, nC <= 2
+int xlam_err_chunks(int N);                      // rows of PM, PJ [chunks][B]
+// u [2N+1][nC][B], x [N+1][ldx][B], lam [N+1][nS][B] -> the ratios rx, rl [N][B], PM (largest per chunk, NaN as +inf), PJ
+// (sum of the cost row's signed estimate per chunk)
+int launch_xlam_err(const ProblemDesc& p, const GridDesc& g, const FbsTables& tx, const XlamErrTables& tq, int batch,
+                    const double* u, const double* x, int ldx, const double* lam, double rtol, double atol, double* rx,
+                    double* rl, double* PM, double* PJ, hipStream_t s);
+// rmax [N]: per interval the larger ratio over the instances with use[b] != 0 (NULL: all); rinst [B]: per instance the
+// largest over the intervals; errJ [B]: the sum of PJ in chunk order; a NaN counts as +inf in the maxima
+int launch_xlam_err_reduce(int N, int batch, const double* rx, const double* rl, const double* PM, const double* PJ,
+                           const int* use, double* rmax, double* rinst, double* errJ, hipStream_t s);
+
 // registry queries (host)
 bool functor_supported(Functor f, int nS, int nC);
 int functor_ntc(Functor f, int nS);

@@ -126,6 +126,7 @@ static std::vector<std::string> kernel_names(int nS, int nC, bool rowsep, bool f
     n[UK_BVP_RMS] = "ocs::k_bvp_rms<ocs::UserP>";
     n[UK_BVP_PROLONG] = "ocs::k_bvp_prolong<ocs::UserP>";
   }
+  if (vector_shape_ok(nS, nC)) n[UK_XLAM_ERR] = "ocs::k_xlam_err<ocs::UserP>";
   return n;
 }
 
@@ -270,18 +271,20 @@ int jit_build(const char* user_src, int nS, int nC, int npar, bool has_cc, bool 
   const bool vec = !rowsep && vector_shape_ok(nS, nC);
   if (vec) src += "#include \"ocs_pipelinev_kernel.hpp\"\n#include \"ocs_vscan_kernel.hpp\"\n#include \"ocs_costate_vscan_kernel.hpp\"\n";
   if (has_cc && vector_shape_ok(nS, nC)) src += "#include \"ocs_bvp_device.hpp\"\n";
+  if (vector_shape_ok(nS, nC)) src += "#include \"ocs_xlam_err_device.hpp\"\n";
 
   const char* hdr_src[] = {src_ocs_device_common_hpp, src_ocs_user_functor_hpp, src_ocs_rk4_kernels_hpp,
                            src_ocs_fbs_device_hpp, src_ocs_pipeline2_kernel_hpp, src_ocs_scan_kernel_hpp,
                            src_ocs_pipelinev_kernel_hpp, src_ocs_vscan_kernel_hpp, src_ocs_fold_kernel_hpp,
                            src_ocs_costate_scan_kernel_hpp, src_ocs_costate_vscan_kernel_hpp,
-                           src_ocs_pipeline2_body_inc, src_ocs_scan_body_inc, src_ocs_bvp_device_hpp};
+                           src_ocs_pipeline2_body_inc, src_ocs_scan_body_inc, src_ocs_bvp_device_hpp,
+                           src_ocs_xlam_err_device_hpp};
   const char* hdr_name[] = {"ocs_device_common.hpp", "ocs_user_functor.hpp", "ocs_rk4_kernels.hpp",
                             "ocs_fbs_device.hpp", "ocs_pipeline2_kernel.hpp", "ocs_scan_kernel.hpp",
                             "ocs_pipelinev_kernel.hpp", "ocs_vscan_kernel.hpp", "ocs_fold_kernel.hpp",
                             "ocs_costate_scan_kernel.hpp", "ocs_costate_vscan_kernel.hpp",
                             "ocs_pipeline2_body.inc", "ocs_scan_body.inc",   // (the two kernels' shared bodies)
-                            "ocs_bvp_device.hpp"};
+                            "ocs_bvp_device.hpp", "ocs_xlam_err_device.hpp"};
   constexpr int kNumHdr = sizeof(hdr_src) / sizeof(hdr_src[0]);
   static_assert(kNumHdr == sizeof(hdr_name) / sizeof(hdr_name[0]), "one name per header");
   const std::vector<std::string> names = kernel_names(nS, nC, rowsep, fold, has_cc);

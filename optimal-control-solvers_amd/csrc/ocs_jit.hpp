@@ -40,6 +40,8 @@ enum UserKernel : int {
   UK_BVP_ASSEMBLE, UK_BVP_NORM,
   // ... and its mesh side: residual estimate of a nodal solution, prolongation to another mesh
   UK_BVP_RMS, UK_BVP_PROLONG,
+  // nS <= 4, nC <= 2: error estimate of the sweep's pass pair (ocs_xlam_err_device.hpp)
+  UK_XLAM_ERR,
   UK_COUNT
 };
 

@@ -96,17 +96,21 @@ def fb_sweep_batch(prob, x0, tspan, options=None, integrator=None):
     interpPts), J, sweeps (0 = not converged), maxChange (nSWEEPS x batch), tspan, interpPts."""
     o, options = _options(options)
     integ = integrator or RK4Integrator(tspan)
-    N = integ.nSTEPS
     x0 = _f(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
     if x0.shape[0] != prob.nS:
         x0 = _f(x0.reshape(prob.nS, -1))
-    batch = x0.shape[1]
-    T0, TF = integ.t[0], integ.t[-1]
-    errorPts = matlab_linspace(T0, TF, o.nERROR_PTS)     # fb_sweep.m:69
-    interpPts = matlab_linspace(T0, TF, o.nINTERP_PTS)   # :70
     u0g = u0e = None
     if "u0" in options:
-        u0g, u0e = _sample_u0(options["u0"], prob, [integ.t, errorPts], batch)
+        errorPts = matlab_linspace(integ.t[0], integ.t[-1], o.nERROR_PTS)     # fb_sweep.m:69
+        u0g, u0e = _sample_u0(options["u0"], prob, [integ.t, errorPts], x0.shape[1])
+    return _sweep(prob, x0, integ, o, u0g, u0e)
+
+
+def _sweep(prob, x0, integ, o, u0g, u0e):
+    """ocs_fb_sweep on the grid of integ: x0 nS x batch, o the FbsOptions, u0g / u0e the first control of every instance on
+    the 2N+1 grid and at the error points (nC x . x batch, column-major) or both None (the lower bound, fb_sweep.m:23)"""
+    N, batch = integ.nSTEPS, x0.shape[1]
+    interpPts = matlab_linspace(integ.t[0], integ.t[-1], o.nINTERP_PTS)   # :70
     x = np.empty((prob.nS, N + 1, batch), order="F")
     lam = np.empty((prob.nS, N + 1, batch), order="F")
     uI = np.empty((prob.nC, o.nINTERP_PTS, batch), order="F")
@@ -169,3 +173,117 @@ def fb_sweep_dev(prob, integ, x0, options=None, u0grid=None, u0err=None, out=Non
                                         _dptr(xaug), _dptr(lam), _dptr(uI), _dptr(J), C.c_void_p(sweeps.data_ptr()),
                                         _dptr(mc), _stream()))
     return {"xaug": xaug, "lam": lam, "u": uI, "J": J, "sweeps": sweeps, "maxChange": mc, "status": status}
+
+
+def x_lam_error(prob, tspan, ugrid, x, lam, RelTol, AbsTol, use=None, integrator=None):
+    """How far x and lam of compute_x_lam(_J) under ugrid -- fixed-step RK4 on tspan -- are from the continuous problem under
+    that control (ocs_x_lam_err): per interval, one step of h against two of h/2 for both passes (the control between its
+    samples is their pchip on the 2N+1 grid; the fine costate steps take their states from the fine state steps, not from the
+    pchip of the nodes, so the coupling error of the pass is seen), as ratios to AbsTol + RelTol max(|v_i|, |v_{i+1}|).
+    ugrid nC x (2N+1) [x batch]; x, lam nS x (N+1) [x batch]; use: batch flags, the instances that count in rmax (default all).
+    Returns {"rx", "rl": N x batch, "rmax": N (the larger ratio over the instances in use), "rinst": batch (the largest over the
+    intervals), "errJ": batch (the estimate of J(tspan) - J(every interval halved), signed)}; a NaN counts as inf in both maxima."""
+    integ = integrator or RK4Integrator(tspan)
+    N, nS, nC = integ.nSTEPS, prob.nS, prob.nC
+    ugrid = np.asarray(ugrid, dtype=np.float64)
+    batch = ugrid.shape[2] if ugrid.ndim == 3 else 1
+    ugrid = _f(ugrid, (nC, 2 * N + 1, batch))
+    x = _f(np.asarray(x, dtype=np.float64), (nS, N + 1, batch))
+    lam = _f(np.asarray(lam, dtype=np.float64), (nS, N + 1, batch))
+    usep = None
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use).ravel() != 0, dtype=np.int32)
+        if use.size != batch:
+            raise ValueError(f"use: expected {batch} flags, got {use.size}")
+        usep = use.ctypes.data_as(ip)
+    rx, rl = np.empty((N, batch), order="F"), np.empty((N, batch), order="F")
+    rmax, rinst, errJ = np.empty(N), np.empty(batch), np.empty(batch)
+    check(lib.ocs_x_lam_err(integ._h, prob._h, batch, _p(ugrid), _p(x), _p(lam), float(RelTol), float(AbsTol), usep, _p(rx),
+                            _p(rl), _p(rmax), _p(rinst), _p(errJ)))
+    return {"rx": rx, "rl": rl, "rmax": rmax, "rinst": rinst, "errJ": errJ}
+
+
+def _refine_mesh(mesh, rmax):
+    """One node in the middle of the intervals with 1 < rmax < 32, two at the thirds of those with rmax >= 32 (a NaN counts as
+    such): the local error of an RK4 step falls by 32 when the step is halved.  Returns the new mesh; nodes are only added."""
+    mesh, r = np.asarray(mesh, dtype=np.float64), np.asarray(rmax, dtype=np.float64)
+    r = np.where(np.isnan(r), np.inf, r)
+    i1, = np.nonzero((r > 1) & (r < 32))
+    i2, = np.nonzero(r >= 32)
+    return np.sort(np.hstack((mesh, 0.5 * (mesh[i1] + mesh[i1 + 1]), (2 * mesh[i2] + mesh[i2 + 1]) / 3,
+                              (mesh[i2] + 2 * mesh[i2 + 1]) / 3)))
+
+
+def _pchip_batch(pts, u, tq):
+    """pchip of every instance's samples u (nC x len(pts) x batch) on pts, at tq: nC x len(tq) x batch"""
+    nC, n, batch = u.shape
+    rows = np.ascontiguousarray(u.transpose(0, 2, 1)).reshape(nC * batch, n)
+    out = vectorInterpolant(pts, rows, "pchip")(tq)
+    return np.asfortranarray(out.reshape(nC, batch, -1).transpose(0, 2, 1))
+
+
+def fb_sweep_adaptive_batch(prob, x0, tspan, options=None):
+    """fb_sweep_batch with an error control of its two passes: sweep on a mesh, estimate the local error of the state and of the
+    costate pass under the control found (x_lam_error), add nodes where it exceeds the tolerance, sweep again from the control
+    found -- until the estimate holds on every interval.  The batch shares the mesh: it is refined wherever any converged
+    instance needs it.
+    options: everything fb_sweep_batch takes, and
+      RelTol, AbsTol  the tolerances of the estimate, default 1e-6 each; they do not warn here.  (The reference's 5e-14,
+                      fb_sweep.m:18-19, is a round-off setting for its 7th/8th-order odevr7 and is not reachable by RK4 meshes.)
+      InitMesh        the first mesh, default tspan
+      MAX_MESH_SIZE   nodes, default 20000: a refinement that would go beyond it is not made
+      u0              belongs to the first mesh
+    Per round: fb_sweep_batch on the mesh; ugrid = pchip of the returned u on interpPts at the 2N+1 grid; x, lam, J =
+    compute_x_lam_J under ugrid; x_lam_error with use = sweeps > 0; intervals with 1 < rmax < 32 get their middle, those with
+    rmax >= 32 (or NaN) their thirds; the next round starts every converged instance from the pchip of its own u on the new
+    grid and error points, the others from the default.
+    Returns the dict of fb_sweep_batch on the last mesh with x, lam, J those under ugrid, and: ugrid, mesh (= tspan), rx, rl
+    (N x batch), errJ, err_ok (per instance: converged and its own largest ratio <= 1), meshes (the node count of every round),
+    mesh_status -- 0: the refinement adds nothing; 1: the next mesh would exceed MAX_MESH_SIZE; 2: no instance converged on a
+    mesh."""
+    options = dict(options or {})
+    rtol, atol = float(options.pop("RelTol", 1e-6)), float(options.pop("AbsTol", 1e-6))
+    max_nodes = int(options.pop("MAX_MESH_SIZE", 20000))
+    mesh = options.pop("InitMesh", None)
+    mesh = _f(tspan if mesh is None else mesh).ravel().copy()
+    if mesh.size < 2 or np.any(np.diff(mesh) <= 0):
+        raise ValueError("fb_sweep_adaptive_batch: need an increasing InitMesh")
+    o, options = _options(options)
+    x0 = _f(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
+    if x0.shape[0] != prob.nS:
+        x0 = _f(x0.reshape(prob.nS, -1))
+    batch = x0.shape[1]
+    errorPts = matlab_linspace(mesh[0], mesh[-1], o.nERROR_PTS)
+    lb = prob.batch_bounds[0] if prob.batch_bounds is not None else np.repeat(prob.ControlBounds[:, 0:1], batch, axis=1)
+    u0g = u0e = None
+    meshes = []
+    while True:
+        integ = RK4Integrator(mesh)
+        if u0g is None and "u0" in options:
+            u0g, u0e = _sample_u0(options.pop("u0"), prob, [integ.t, errorPts], batch)
+        res = _sweep(prob, x0, integ, o, u0g, u0e)
+        meshes.append(int(mesh.size))
+        conv = res["sweeps"] > 0
+        ugrid = _pchip_batch(res["interpPts"], res["u"], integ.t)
+        x, lam, J = compute_x_lam_J(prob, x0, mesh, ugrid, integrator=integ)
+        est = x_lam_error(prob, mesh, ugrid, x, lam, rtol, atol, use=conv, integrator=integ)
+        if not conv.any():
+            status = 2
+            break
+        new = _refine_mesh(mesh, est["rmax"])
+        if new.size == mesh.size:
+            status = 0
+            break
+        if new.size > max_nodes:
+            status = 1
+            break
+        t2 = np.zeros(2 * new.size - 1)          # the 2N+1 grid of the next integrator (RK4Integrator.m:16-25)
+        t2[0::2], t2[1::2] = new, (new[:-1] + new[1:]) / 2
+        u0g, u0e = _pchip_batch(res["interpPts"], res["u"], t2), _pchip_batch(res["interpPts"], res["u"], errorPts)
+        for arr in (u0g, u0e):
+            arr[:, :, ~conv] = lb[:, None, ~conv]
+        del integ
+        mesh = new
+    res.update(x=x, lam=lam, J=J, ugrid=ugrid, mesh=res["tspan"], rx=est["rx"], rl=est["rl"], errJ=est["errJ"],
+               err_ok=conv & (est["rinst"] <= 1), meshes=meshes, mesh_status=status)
+    return res
