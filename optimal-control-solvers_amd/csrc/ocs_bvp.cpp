@@ -26,10 +26,9 @@ struct ocs_bvp_state {
   // host entry point
   DevBuf x0, y0, u0, y, xaug, lam, uint_, J, iters, conv, res, stage;
   // the mesh side (ocs_bvp_rms, ocs_bvp_prolong): rms [N][B] where the caller wants none, its chunk maxima, the Lobatto
-  // points of the grid with their time coefficients (those follow the problem like TUI), the prolongation map
-  DevBuf rms, PM, TL, TCL, TUL, pidx, ptheta;
-  const ocs_problem_s* tl_prob = nullptr;
-  unsigned long long tl_version = 0;
+  // points of the grid with their time coefficients, the prolongation map
+  DevBuf rms, PM, pidx, ptheta;
+  TcoefAt lobatto;
   // ... and their host entry points
   DevBuf use, rmsmax, rmsinst, ynew;
 };
@@ -264,33 +263,25 @@ int ocs_bvp_rms_dev(ocs_integrator g, ocs_problem p, int batch, const double* yn
   ocs_bvp_state* f = g->bvp;
   const int N = g->N;
   const size_t B = (size_t)batch;
-  if (!f->TL.p) {   // t_m -/+ (h/2) sqrt(3/7) in fp64, like the grid itself: the same numbers for every implementation
-    std::vector<double> tl((size_t)2 * N);
+  std::vector<double> tl;
+  if (!f->lobatto.T.p) {   // t_m -/+ (h/2) sqrt(3/7) in fp64, like the grid itself: the same numbers for every implementation
+    tl.resize((size_t)2 * N);
     const double s37 = std::sqrt(3.0 / 7.0);
     for (int i = 0; i < N; ++i) {
       const double d = g->h[i] / 2 * s37;
       tl[2 * (size_t)i] = g->t[2 * (size_t)i + 1] - d;
       tl[2 * (size_t)i + 1] = g->t[2 * (size_t)i + 1] + d;
     }
-    OCS_TRY(f->TL.ensure(sizeof(double) * tl.size()));
-    HIP_TRY(hipMemcpy(f->TL.p, tl.data(), sizeof(double) * tl.size(), hipMemcpyHostToDevice));
-    f->tl_prob = nullptr;
   }
-  const ProblemDesc pd = describe(p);
-  if (f->tl_prob != p || f->tl_version != p->version) {
-    OCS_TRY(f->TCL.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntc(p->functor, p->nS))));
-    OCS_TRY(f->TUL.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntu(p->functor, p->nS))));
-    LAUNCH_TRY(launch_tcoef_at(pd, 2 * N, f->TL.d(), f->TCL.d(), f->TUL.d(), s));
-    f->tl_prob = p;
-    f->tl_version = p->version;
-  }
+  OCS_TRY(f->lobatto.ensure(p, 2 * N, tl.data(), s));
   if (!rms) {
     OCS_TRY(f->rms.ensure(sizeof(double) * (size_t)N * B));
     rms = f->rms.d();
   }
-  OCS_TRY(f->PM.ensure(sizeof(double) * (size_t)bvp_chunks(N) * B));
-  LAUNCH_TRY(launch_bvp_rms(pd, describe(g), batch, f->TCL.d(), f->TUL.d(), ynodes, rms, f->PM.d(), s));
-  LAUNCH_TRY(launch_bvp_rms_reduce(N, batch, rms, f->PM.d(), use, rmsmax, rmsinst, s));
+  const int nparts = bvp_chunks(N);
+  OCS_TRY(f->PM.ensure(sizeof(double) * (size_t)nparts * B));
+  LAUNCH_TRY(launch_bvp_rms(describe(p), describe(g), batch, f->lobatto.TC.d(), f->lobatto.TU.d(), ynodes, rms, f->PM.d(), s));
+  LAUNCH_TRY(launch_interval_reduce(N, batch, nparts, rms, nullptr, f->PM.d(), nullptr, use, rmsmax, rmsinst, nullptr, s));
   return OCS_OK;
 }
 
@@ -308,20 +299,14 @@ int ocs_bvp_rms(ocs_integrator g, ocs_problem p, int batch, const double* ynodes
   hipStream_t s = g->stream;
   HIP_TRY(hipStreamSynchronize(s));   // (the stage buffer may still be in use)
   OCS_TRY(stage_in(f->stage, f->y, ynodes, nY * (N + 1), batch, s));
-  if (use) {
-    OCS_TRY(f->use.ensure(sizeof(int) * B));
-    HIP_TRY(hipMemcpyAsync(f->use.p, use, sizeof(int) * B, hipMemcpyHostToDevice, s));
-  }
+  const int* duse;
+  OCS_TRY(stage_flags(f->use, use, batch, s, &duse));
   OCS_TRY(f->rms.ensure(sizeof(double) * (size_t)N * B));
   OCS_TRY(f->rmsmax.ensure(sizeof(double) * (size_t)N));
   OCS_TRY(f->rmsinst.ensure(sizeof(double) * B));
-  OCS_TRY(ocs_bvp_rms_dev(g, p, batch, f->y.d(), use ? (const int*)f->use.p : nullptr, f->rms.d(), f->rmsmax.d(),
-                          f->rmsinst.d(), s));
+  OCS_TRY(ocs_bvp_rms_dev(g, p, batch, f->y.d(), duse, f->rms.d(), f->rmsmax.d(), f->rmsinst.d(), s));
   if (rms) OCS_TRY(stage_out(f->stage, f->rms.d(), rms, N, batch, s));
-  HIP_TRY(hipMemcpyAsync(rmsmax, f->rmsmax.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(rmsinst, f->rmsinst.p, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return OCS_OK;
+  return fetch({{rmsmax, f->rmsmax, (size_t)N}, {rmsinst, f->rmsinst, B}}, s);
 }
 
 int ocs_bvp_prolong_dev(ocs_integrator g_old, ocs_problem p, int batch, const double* ynodes_old, int nnew, const int* idx,

@@ -319,7 +319,7 @@ int launch_bvp_norm(const ProblemDesc& p, const GridDesc& g, const BvpIterate& a
 }
 
 // ---------------------------------------------------------------------------------------
-// the mesh side: residual estimate, its two maxima, prolongation
+// the mesh side: residual estimate (its two maxima: launch_interval_reduce, ocs_kernels.hip), prolongation
 // ---------------------------------------------------------------------------------------
 int launch_bvp_rms(const ProblemDesc& p, const GridDesc& g, int batch, const double* TCL, const double* TUL, const double* y,
                    double* rms, double* PM, hipStream_t s) {
@@ -331,42 +331,6 @@ int launch_bvp_rms(const ProblemDesc& p, const GridDesc& g, int batch, const dou
     return jit_launch(p.user, UK_BVP_RMS, grid, dim3(64), args, s);
   }
   if (!for_logistic<1, 2, 3, 4>(p.nS, [&](auto P) { k_bvp_rms<decltype(P)><<<grid, dim3(64), 0, s>>>(a); })) return -1;
-  return hip_rc(hipGetLastError());
-}
-
-// Workgroups 0 .. N-1: rmsmax[i] = the largest rms[i][b] over the instances with use[b] != 0 (use == NULL: all; none: 0).
-// The workgroups behind them, one thread per instance: rmsinst[b] = the largest of the instance's chunk maxima PM.  A NaN
-// counts as +inf on both sides ("exceeds every tolerance"); an instance's NaN reaches rmsmax only where it is in use, and
-// never another instance's rmsinst.  Maxima only, no floating-point atomics: the order of the reduction does not show.
-__global__ __launch_bounds__(256) void k_bvp_rms_reduce(int N, int batch, int nparts, const double* __restrict__ rms,
-                                                        const double* __restrict__ PM, const int* __restrict__ use,
-                                                        double* __restrict__ rmsmax, double* __restrict__ rmsinst) {
-  const size_t B = (size_t)batch;
-  if ((int)blockIdx.x >= N) {
-    const int b = (blockIdx.x - N) * 256 + threadIdx.x;
-    if (b >= batch) return;
-    double m = 0.0;
-    for (int q = 0; q < nparts; ++q) m = fmax(m, PM[(size_t)q * B + b]);
-    rmsinst[b] = m;
-    return;
-  }
-  __shared__ double part[4];
-  const double* row = rms + (size_t)blockIdx.x * B;
-  double m = 0.0;
-  for (int b = threadIdx.x; b < batch; b += 256) {
-    if (use && use[b] == 0) continue;
-    const double v = row[b];
-    m = fmax(m, v == v ? v : __builtin_inf());
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) rmsmax[blockIdx.x] = fmax(fmax(part[0], part[1]), fmax(part[2], part[3]));
-}
-int launch_bvp_rms_reduce(int N, int batch, const double* rms, const double* PM, const int* use, double* rmsmax,
-                          double* rmsinst, hipStream_t s) {
-  k_bvp_rms_reduce<<<dim3(N + (batch + 255) / 256), dim3(256), 0, s>>>(N, batch, bvp_chunks(N), rms, PM, use, rmsmax, rmsinst);
   return hip_rc(hipGetLastError());
 }
 

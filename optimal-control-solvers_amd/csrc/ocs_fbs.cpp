@@ -43,12 +43,10 @@ struct ocs_fbs_state {
   // work arrays
   DevBuf xaug, xmid, lam, lmid, ugrid, uerr, uint_, J, usel, status, maxchange, nactive, x0, stage, metric, anyvalid, dump;
   // the error estimate (ocs_x_lam_err): pchip tables of the grid t (spacings, slope weights), the quarter points (local
-  // coordinates, times; their time coefficients follow the problem like TUI), ratios where the caller wants none, chunk
-  // partials -- and the arrays of its host entry point
-  DevBuf eHG, eW1G, eW2G, eSQ, eTQ, eTCQ, eTUQ, erx, erl, ePM, ePJ;
-  bool etables = false;
-  const ocs_problem_s* etc_prob = nullptr;
-  unsigned long long etc_version = 0;
+  // coordinates; times and their time coefficients), ratios where the caller wants none, chunk partials -- and the arrays of
+  // its host entry point
+  DevBuf eHG, eW1G, eW2G, eSQ, erx, erl, ePM, ePJ;
+  TcoefAt quarter;
   DevBuf eu, ex, elam, euse, ermax, erinst, eerrJ;
   ~ocs_fbs_state() {
     if (lq_event) (void)hipEventDestroy(lq_event);
@@ -58,12 +56,6 @@ struct ocs_fbs_state {
 };
 
 void ocs_fbs_state_free(ocs_fbs_state* s) { delete s; }
-
-static int upload(DevBuf& d, const void* src, size_t bytes) {
-  OCS_TRY(d.ensure(bytes ? bytes : 8));
-  if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-  return OCS_OK;
-}
 
 static int ensure_tables(ocs_integrator_s* g) {
   if (!g->fbs) g->fbs = new ocs_fbs_state();
@@ -837,8 +829,10 @@ int ocs_x_lam_err_dev(ocs_integrator g, ocs_problem p, int batch, const double* 
   ocs_fbs_state* f = g->fbs;
   const int N = g->N, nG = 2 * N + 1;
   const size_t B = (size_t)batch;
-  if (!f->etables) {   // everything in fp64 from the grid, like the grid itself: the same numbers for every implementation
-    std::vector<double> hg((size_t)nG - 1), w1(nG), w2(nG), tq((size_t)2 * N), sq((size_t)2 * N);
+  std::vector<double> tq;
+  if (!f->quarter.T.p) {   // everything in fp64 from the grid, like the grid itself: the same numbers for every implementation
+    std::vector<double> hg((size_t)nG - 1), w1(nG), w2(nG), sq((size_t)2 * N);
+    tq.resize((size_t)2 * N);
     for (int j = 0; j + 1 < nG; ++j) hg[j] = g->t[(size_t)j + 1] - g->t[j];
     pchip_weights(nG, hg.data(), w1.data(), w2.data());
     for (int i = 0; i < N; ++i) {
@@ -850,19 +844,9 @@ int ocs_x_lam_err_dev(ocs_integrator g, ocs_problem p, int batch, const double* 
     OCS_TRY(upload(f->eHG, hg.data(), sizeof(double) * hg.size()));
     OCS_TRY(upload(f->eW1G, w1.data(), sizeof(double) * w1.size()));
     OCS_TRY(upload(f->eW2G, w2.data(), sizeof(double) * w2.size()));
-    OCS_TRY(upload(f->eTQ, tq.data(), sizeof(double) * tq.size()));
     OCS_TRY(upload(f->eSQ, sq.data(), sizeof(double) * sq.size()));
-    f->etables = true;
-    f->etc_prob = nullptr;
   }
-  const ProblemDesc pd = describe(p);
-  if (f->etc_prob != p || f->etc_version != p->version) {
-    OCS_TRY(f->eTCQ.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntc(p->functor, p->nS))));
-    OCS_TRY(f->eTUQ.ensure(sizeof(double) * (size_t)2 * N * std::max(1, functor_ntu(p->functor, p->nS))));
-    LAUNCH_TRY(launch_tcoef_at(pd, 2 * N, f->eTQ.d(), f->eTCQ.d(), f->eTUQ.d(), s));
-    f->etc_prob = p;
-    f->etc_version = p->version;
-  }
+  OCS_TRY(f->quarter.ensure(p, 2 * N, tq.data(), s));   // (uploads the times last: a failure above is met again)
   if (!rx) {
     OCS_TRY(f->erx.ensure(sizeof(double) * (size_t)N * B));
     rx = f->erx.d();
@@ -871,13 +855,13 @@ int ocs_x_lam_err_dev(ocs_integrator g, ocs_problem p, int batch, const double* 
     OCS_TRY(f->erl.ensure(sizeof(double) * (size_t)N * B));
     rl = f->erl.d();
   }
-  const size_t parts = (size_t)xlam_err_chunks(N);
-  OCS_TRY(f->ePM.ensure(sizeof(double) * parts * B));
-  OCS_TRY(f->ePJ.ensure(sizeof(double) * parts * B));
-  const XlamErrTables tq{f->eHG.d(), f->eW1G.d(), f->eW2G.d(), f->eSQ.d(), f->eTCQ.d()};
-  LAUNCH_TRY(launch_xlam_err(pd, describe(g), tabs(g), tq, batch, ugrid, x, ldx, lam, RelTol, AbsTol, rx, rl, f->ePM.d(),
-                             f->ePJ.d(), s));
-  LAUNCH_TRY(launch_xlam_err_reduce(N, batch, rx, rl, f->ePM.d(), f->ePJ.d(), use, rmax, rinst, errJ, s));
+  const int nparts = xlam_err_chunks(N);
+  OCS_TRY(f->ePM.ensure(sizeof(double) * (size_t)nparts * B));
+  OCS_TRY(f->ePJ.ensure(sizeof(double) * (size_t)nparts * B));
+  const XlamErrTables te{f->eHG.d(), f->eW1G.d(), f->eW2G.d(), f->eSQ.d(), f->quarter.TC.d()};
+  LAUNCH_TRY(launch_xlam_err(describe(p), describe(g), tabs(g), te, batch, ugrid, x, ldx, lam, RelTol, AbsTol, rx, rl,
+                             f->ePM.d(), f->ePJ.d(), s));
+  LAUNCH_TRY(launch_interval_reduce(N, batch, nparts, rx, rl, f->ePM.d(), f->ePJ.d(), use, rmax, rinst, errJ, s));
   return OCS_OK;
 }
 
@@ -901,25 +885,18 @@ int ocs_x_lam_err(ocs_integrator g, ocs_problem p, int batch, const double* ugri
   OCS_TRY(stage_in(f->stage, f->ex, x, nS * (N + 1), batch, s));
   HIP_TRY(hipStreamSynchronize(s));
   OCS_TRY(stage_in(f->stage, f->elam, lam, nS * (N + 1), batch, s));
-  if (use) {
-    OCS_TRY(f->euse.ensure(sizeof(int) * B));
-    HIP_TRY(hipMemcpyAsync(f->euse.p, use, sizeof(int) * B, hipMemcpyHostToDevice, s));
-  }
+  const int* duse;
+  OCS_TRY(stage_flags(f->euse, use, batch, s, &duse));
   OCS_TRY(f->erx.ensure(sizeof(double) * (size_t)N * B));
   OCS_TRY(f->erl.ensure(sizeof(double) * (size_t)N * B));
   OCS_TRY(f->ermax.ensure(sizeof(double) * (size_t)N));
   OCS_TRY(f->erinst.ensure(sizeof(double) * B));
   OCS_TRY(f->eerrJ.ensure(sizeof(double) * B));
-  OCS_TRY(ocs_x_lam_err_dev(g, p, batch, f->eu.d(), f->ex.d(), nS, f->elam.d(), RelTol, AbsTol,
-                            use ? (const int*)f->euse.p : nullptr, f->erx.d(), f->erl.d(), f->ermax.d(), f->erinst.d(),
-                            f->eerrJ.d(), s));
+  OCS_TRY(ocs_x_lam_err_dev(g, p, batch, f->eu.d(), f->ex.d(), nS, f->elam.d(), RelTol, AbsTol, duse, f->erx.d(), f->erl.d(),
+                            f->ermax.d(), f->erinst.d(), f->eerrJ.d(), s));
   if (rx) OCS_TRY(stage_out(f->stage, f->erx.d(), rx, N, batch, s));
   if (rl) OCS_TRY(stage_out(f->stage, f->erl.d(), rl, N, batch, s));
-  HIP_TRY(hipMemcpyAsync(rmax, f->ermax.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(rinst, f->erinst.p, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(errJ, f->eerrJ.p, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return OCS_OK;
+  return fetch({{rmax, f->ermax, (size_t)N}, {rinst, f->erinst, B}, {errJ, f->eerrJ, B}}, s);
 }
 
 }  // extern "C"

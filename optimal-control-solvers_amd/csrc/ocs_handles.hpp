@@ -7,11 +7,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -113,6 +115,13 @@ struct DevBuf {
   double* d() const { return static_cast<double*>(p); }
 };
 
+// a host table to a buffer of its size (never an empty one); returns when the copy is done
+inline int upload(DevBuf& d, const void* src, size_t bytes) {
+  OCS_TRY(d.ensure(bytes ? bytes : 8));
+  if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+  return OCS_OK;
+}
+
 // Host staging: a MATLAB-shaped host array (`per` doubles per trajectory, trajectory-major) to / from a batch-minor device
 // array, through the caller's ONE stage buffer on the caller's stream.  stage_out waits for the stream: the host array is
 // complete and the stage buffer free again on return.  stage_in does not wait; a caller whose stage buffer may still be in
@@ -130,6 +139,26 @@ inline int stage_out(DevBuf& stage, const double* src, double* host, int per, in
   OCS_TRY(stage.ensure(bytes));
   LAUNCH_TRY(launch_to_traj_major(src, stage.d(), per, batch, s));
   HIP_TRY(hipMemcpyAsync(host, stage.p, bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return OCS_OK;
+}
+// The caller's batch flags (`use` of the estimates) to the device on s: *dev is the device copy, NULL for use == NULL.
+inline int stage_flags(DevBuf& dst, const int* use, int batch, hipStream_t s, const int** dev) {
+  *dev = nullptr;
+  if (!use) return OCS_OK;
+  OCS_TRY(dst.ensure(sizeof(int) * (size_t)batch));
+  HIP_TRY(hipMemcpyAsync(dst.p, use, sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, s));
+  *dev = (const int*)dst.p;
+  return OCS_OK;
+}
+// Small result vectors (n doubles each, no layout to change) back to the host on s; waits for the stream like stage_out.
+struct Fetch {
+  double* host;
+  const DevBuf& dev;
+  size_t n;
+};
+inline int fetch(std::initializer_list<Fetch> vectors, hipStream_t s) {
+  for (const Fetch& v : vectors) HIP_TRY(hipMemcpyAsync(v.host, v.dev.p, sizeof(double) * v.n, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return OCS_OK;
 }
@@ -322,6 +351,29 @@ inline ProblemDesc describe(const ocs_problem_s* p) {
   d.version = p->version;
   return d;
 }
+
+// The time coefficients of a problem at n extra times of a grid (launch_tcoef_at): TC [n][NTC], TU [n][NTU].  The times are a
+// property of the grid and go up once per handle; the tables follow (problem, version) like the integrator's own (bind_problem).
+struct TcoefAt {
+  DevBuf T, TC, TU;
+  const ocs_problem_s* prob = nullptr;
+  unsigned long long version = 0;
+  // times: n host values, read only while T is empty; the tables are rebuilt on s
+  int ensure(const ocs_problem_s* p, int n, const double* times, hipStream_t s) {
+    if (!T.p) {
+      OCS_TRY(upload(T, times, sizeof(double) * (size_t)n));
+      prob = nullptr;
+    }
+    if (prob != p || version != p->version) {
+      OCS_TRY(TC.ensure(sizeof(double) * (size_t)n * std::max(1, functor_ntc(p->functor, p->nS))));
+      OCS_TRY(TU.ensure(sizeof(double) * (size_t)n * std::max(1, functor_ntu(p->functor, p->nS))));
+      LAUNCH_TRY(launch_tcoef_at(describe(p), n, T.d(), TC.d(), TU.d(), s));
+      prob = p;
+      version = p->version;
+    }
+    return OCS_OK;
+  }
+};
 
 inline int upload_grid(ocs_integrator_s* g) {
   if (g->grid_uploaded) return OCS_OK;

@@ -406,10 +406,6 @@ int launch_bvp_converged(int batch, const int* status, int* converged, hipStream
 int launch_tcoef_at(const ProblemDesc& p, int nq, const double* tq, double* TCQ, double* TUQ, hipStream_t s);
 int launch_bvp_rms(const ProblemDesc& p, const GridDesc& g, int batch, const double* TCL, const double* TUL, const double* y,
                    double* rms, double* PM, hipStream_t s);
-// rmsmax [N]: per interval the largest rms over the instances with use[b] != 0 (NULL: all); rmsinst [B]: per instance the
-// largest over the intervals; a NaN counts as +inf
-int launch_bvp_rms_reduce(int N, int batch, const double* rms, const double* PM, const int* use, double* rmsmax,
-                          double* rmsinst, hipStream_t s);
 // the Hermite interpolant of y on the grid of g at nnew points (interval idx, position theta in it): ynew [nnew][2 nS][B]
 int launch_bvp_prolong(const ProblemDesc& p, const GridDesc& g, int batch, const double* y, int nnew, const int* idx,
                        const double* theta, double* ynew, hipStream_t s);
@@ -429,10 +425,13 @@ int xlam_err_chunks(int N);                      // rows of PM, PJ [chunks][B]
 int launch_xlam_err(const ProblemDesc& p, const GridDesc& g, const FbsTables& tx, const XlamErrTables& tq, int batch,
                     const double* u, const double* x, int ldx, const double* lam, double rtol, double atol, double* rx,
                     double* rl, double* PM, double* PJ, hipStream_t s);
-// rmax [N]: per interval the larger ratio over the instances with use[b] != 0 (NULL: all); rinst [B]: per instance the
-// largest over the intervals; errJ [B]: the sum of PJ in chunk order; a NaN counts as +inf in the maxima
-int launch_xlam_err_reduce(int N, int batch, const double* rx, const double* rl, const double* PM, const double* PJ,
-                           const int* use, double* rmax, double* rinst, double* errJ, hipStream_t s);
+
+// what both estimates reduce their ratios [N][B] and chunk partials [nparts][B] with (ocs_kernels.hip), use [B] or NULL (all):
+// rmax[i]  = max over instances in use of max(r0[i][b], r1 ? r1[i][b] : r0[i][b]), NaN -> +inf, none in use -> 0
+// rinst[b] = max over chunks of PM[q][b];   sum[b] = PS[q][b] added from 0.0 in chunk order (PS, sum may be NULL together)
+// Instantiated for the two forms in use: r0 alone without a sum, r0 and r1 with it (any other: -1).
+int launch_interval_reduce(int N, int batch, int nparts, const double* r0, const double* r1, const double* PM,
+                           const double* PS, const int* use, double* rmax, double* rinst, double* sum, hipStream_t s);
 
 // registry queries (host)
 bool functor_supported(Functor f, int nS, int nC);

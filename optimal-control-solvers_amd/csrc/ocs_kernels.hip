@@ -552,6 +552,59 @@ int launch_traj_status(const double* J, int n, int* status, hipStream_t s) {
   return hip_rc(hipGetLastError());
 }
 
+// The reduction behind the per-interval estimates of the mesh drivers (ocs_bvp_rms: one ratio array, no sum; ocs_x_lam_err: two
+// and the sum).  Workgroups 0 .. N-1: rmax[i] = the largest of r0[i][b] (and r1[i][b]) over the instances with use[b] != 0
+// (use == NULL: all; none: 0).  The workgroups behind them, one thread per instance: rinst[b] = the largest of the instance's
+// chunk maxima PM, sum[b] = its chunk sums PS added in chunk order.  A NaN counts as +inf in both maxima ("exceeds every
+// tolerance"); an instance's NaN reaches rmax only where it is in use, and never another instance's rinst or sum.  Maxima, and
+// one thread's sum in a fixed order: no floating-point atomics, the order of the reduction does not show.  The per-instance
+// threads walk their chunks one load latency at a time and are the last to finish: the sum rides in the loop of the maximum.
+template <bool Two, bool Sum>
+__global__ __launch_bounds__(256) void k_interval_reduce(int N, int batch, int nparts, const double* __restrict__ r0,
+                                                         const double* __restrict__ r1, const double* __restrict__ PM,
+                                                         const double* __restrict__ PS, const int* __restrict__ use,
+                                                         double* __restrict__ rmax, double* __restrict__ rinst,
+                                                         double* __restrict__ sum) {
+  const size_t B = (size_t)batch;
+  if ((int)blockIdx.x >= N) {
+    const int b = (blockIdx.x - N) * 256 + threadIdx.x;
+    if (b >= batch) return;
+    double m = 0.0, sj = 0.0;
+    for (int q = 0; q < nparts; ++q) {
+      m = fmax(m, PM[(size_t)q * B + b]);
+      if (Sum) sj += PS[(size_t)q * B + b];
+    }
+    rinst[b] = m;
+    if (Sum) sum[b] = sj;
+    return;
+  }
+  __shared__ double part[4];
+  const double* row0 = r0 + (size_t)blockIdx.x * B;
+  const double* row1 = Two ? r1 + (size_t)blockIdx.x * B : row0;
+  double m = 0.0;
+  for (int b = threadIdx.x; b < batch; b += 256) {
+    if (use && use[b] == 0) continue;
+    const double v0 = row0[b], v1 = Two ? row1[b] : v0;
+    m = fmax(m, (v0 == v0 && v1 == v1) ? fmax(v0, v1) : __builtin_inf());
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) rmax[blockIdx.x] = fmax(fmax(part[0], part[1]), fmax(part[2], part[3]));
+}
+int launch_interval_reduce(int N, int batch, int nparts, const double* r0, const double* r1, const double* PM,
+                           const double* PS, const int* use, double* rmax, double* rinst, double* sum, hipStream_t s) {
+  const dim3 grid(N + (batch + 255) / 256), block(256);
+  if (r1 && PS)
+    k_interval_reduce<true, true><<<grid, block, 0, s>>>(N, batch, nparts, r0, r1, PM, PS, use, rmax, rinst, sum);
+  else if (!r1 && !PS)
+    k_interval_reduce<false, false><<<grid, block, 0, s>>>(N, batch, nparts, r0, r1, PM, PS, use, rmax, rinst, sum);
+  else
+    return -1;   // (instantiated for the two estimates there are)
+  return hip_rc(hipGetLastError());
+}
+
 // one workgroup: the post-reductions of a shard's objectives (ocs_multi.cpp)
 // (mask: optional, entries <= 0 are left out -- the sweep index of fb_sweep, 0 = not converged)
 __global__ __launch_bounds__(256) void k_objective_stats(const double* __restrict__ J, int n, int lo, double* __restrict__ out,

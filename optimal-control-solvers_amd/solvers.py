@@ -17,6 +17,7 @@ from ._lib import OcsError, check, lib
 from .control import PWLinearControl
 from .integrator import RK4Integrator, _dptr, _stream
 from .interp import vectorInterpolant
+from .mesh import _prolong_map, adapt_mesh, use_flags, x0_batch
 from .problem import _f, _p
 
 
@@ -414,9 +415,7 @@ def bvp_solver_batch(prob, x0, tspan, options=None, integrator=None):
     integ = integrator or RK4Integrator(tspan)
     N = integ.nSTEPS
     nS, nC = prob.nS, prob.nC
-    x0 = _f(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
-    if x0.shape[0] != nS:
-        x0 = _f(x0.reshape(nS, -1))
+    x0 = x0_batch(prob, x0)
     batch = x0.shape[1]
     interpPts = matlab_linspace(integ.t[0], integ.t[-1], o.nINTERP_PTS)           # :99
     y0 = u0g = None
@@ -446,7 +445,6 @@ def bvp_residuals(prob, tspan, y, use=None, integrator=None):
     the five-point Lobatto rule -- estimate_rms_residuals of scipy.integrate.solve_bvp, bvp4c's error estimate.
     use: batch flags, the instances that count in rmsmax (default all).  Returns {"rms": N x batch, "rmsmax": N (largest
     over the instances in use), "rmsinst": batch (largest over the intervals)}; a NaN counts as inf in both maxima."""
-    from ._lib import ip
     integ = integrator or RK4Integrator(tspan)
     N, nS = integ.nSTEPS, prob.nS
     y = np.asarray(y, dtype=np.float64)
@@ -454,37 +452,11 @@ def bvp_residuals(prob, tspan, y, use=None, integrator=None):
         y = y[:, :, None]
     batch = y.shape[2]
     y = _f(y, (2 * nS, N + 1, batch))
-    usep = None
-    if use is not None:
-        use = np.ascontiguousarray(np.asarray(use).ravel() != 0, dtype=np.int32)
-        if use.size != batch:
-            raise ValueError(f"use: expected {batch} flags, got {use.size}")
-        usep = use.ctypes.data_as(ip)
+    use, usep = use_flags(use, batch)
     rms = np.empty((N, batch), order="F")
     rmsmax, rmsinst = np.empty(N), np.empty(batch)
     check(lib.ocs_bvp_rms(integ._h, prob._h, batch, _p(y), usep, _p(rms), _p(rmsmax), _p(rmsinst)))
     return {"rms": rms, "rmsmax": rmsmax, "rmsinst": rmsinst}
-
-
-def _refine_mesh(mesh, rmsmax, tol):
-    """modify_mesh of scipy.integrate.solve_bvp with its rule for what to insert: one node in the middle of the intervals
-    with tol < rmsmax < 100 tol, two nodes at the thirds of those with rmsmax >= 100 tol (a NaN counts as such).  Returns
-    the new mesh; nodes are only added."""
-    mesh, r = np.asarray(mesh, dtype=np.float64), np.asarray(rmsmax, dtype=np.float64)
-    r = np.where(np.isnan(r), np.inf, r)
-    i1, = np.nonzero((r > tol) & (r < 100 * tol))
-    i2, = np.nonzero(r >= 100 * tol)
-    return np.sort(np.hstack((mesh, 0.5 * (mesh[i1] + mesh[i1 + 1]), (2 * mesh[i2] + mesh[i2 + 1]) / 3,
-                              (mesh[i2] + 2 * mesh[i2 + 1]) / 3)))
-
-
-def _prolong_map(old, new):
-    """Where the nodes of `new` lie on the mesh `old`: (idx int32, theta) with new = old[idx] + theta (old[idx + 1] - old[idx]),
-    0 <= theta <= 1; a node of `old` has theta 0 (the last one: theta 1 in the last interval)."""
-    old, new = np.asarray(old, dtype=np.float64), np.asarray(new, dtype=np.float64)
-    idx = np.clip(np.searchsorted(old, new, side="right") - 1, 0, old.size - 2)
-    theta = (new - old[idx]) / (old[idx + 1] - old[idx])
-    return np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(theta)
 
 
 def bvp_prolong(prob, tspan, y, new_tspan, integrator=None):
@@ -530,27 +502,15 @@ def bvp_solver_adaptive_batch(prob, x0, tspan, options=None):
     mesh = matlab_linspace(tspan[0], tspan[-1], 11) if mesh is None else _f(mesh).ravel().copy()
     if not tol > 0 or mesh.size < 2 or np.any(np.diff(mesh) <= 0):
         raise ValueError("bvp_solver_adaptive_batch: need bvpRelTol > 0 and an increasing InitMesh")
-    meshes = []
-    while True:
-        integ = RK4Integrator(mesh)
+
+    def solve_round(mesh, integ):
         res = bvp_solver_batch(prob, x0, mesh, options, integrator=integ)
-        meshes.append(int(mesh.size))
         est = bvp_residuals(prob, mesh, res["y"], use=res["converged"], integrator=integ)
-        if not res["converged"].any():
-            status = 2
-            break
-        new = _refine_mesh(mesh, est["rmsmax"], tol)
-        if new.size == mesh.size:
-            status = 0
-            break
-        if new.size > max_nodes:
-            status = 1
-            break
-        start = bvp_prolong(prob, mesh, res["y"], new, integrator=integ)
-        del integ                                    # (the handle's bvp workspace goes with it)
-        options.pop("u0", None)
-        options["y0"] = start
-        mesh = new
-    res.update(mesh=res["tspan"], rms=est["rms"], rms_ok=res["converged"] & (est["rmsinst"] <= tol), mesh_status=status,
-               meshes=meshes)
-    return res
+        res.update(mesh=res["tspan"], rms=est["rms"], rms_ok=res["converged"] & (est["rmsinst"] <= tol))
+
+        def restart(new):
+            options.pop("u0", None)
+            options["y0"] = bvp_prolong(prob, mesh, res["y"], new, integrator=integ)
+        return res, res["converged"], est["rmsmax"], restart
+
+    return adapt_mesh(mesh, max_nodes, tol, 100 * tol, solve_round)

@@ -14,6 +14,7 @@ import torch
 from ._lib import FbsOptions, check, ip, lib
 from .integrator import RK4Integrator, _dptr, _stream
 from .interp import vectorInterpolant
+from .mesh import adapt_mesh, use_flags, x0_batch
 from .problem import _f, _p
 
 
@@ -96,9 +97,7 @@ def fb_sweep_batch(prob, x0, tspan, options=None, integrator=None):
     interpPts), J, sweeps (0 = not converged), maxChange (nSWEEPS x batch), tspan, interpPts."""
     o, options = _options(options)
     integ = integrator or RK4Integrator(tspan)
-    x0 = _f(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
-    if x0.shape[0] != prob.nS:
-        x0 = _f(x0.reshape(prob.nS, -1))
+    x0 = x0_batch(prob, x0)
     u0g = u0e = None
     if "u0" in options:
         errorPts = matlab_linspace(integ.t[0], integ.t[-1], o.nERROR_PTS)     # fb_sweep.m:69
@@ -190,28 +189,12 @@ def x_lam_error(prob, tspan, ugrid, x, lam, RelTol, AbsTol, use=None, integrator
     ugrid = _f(ugrid, (nC, 2 * N + 1, batch))
     x = _f(np.asarray(x, dtype=np.float64), (nS, N + 1, batch))
     lam = _f(np.asarray(lam, dtype=np.float64), (nS, N + 1, batch))
-    usep = None
-    if use is not None:
-        use = np.ascontiguousarray(np.asarray(use).ravel() != 0, dtype=np.int32)
-        if use.size != batch:
-            raise ValueError(f"use: expected {batch} flags, got {use.size}")
-        usep = use.ctypes.data_as(ip)
+    use, usep = use_flags(use, batch)
     rx, rl = np.empty((N, batch), order="F"), np.empty((N, batch), order="F")
     rmax, rinst, errJ = np.empty(N), np.empty(batch), np.empty(batch)
     check(lib.ocs_x_lam_err(integ._h, prob._h, batch, _p(ugrid), _p(x), _p(lam), float(RelTol), float(AbsTol), usep, _p(rx),
                             _p(rl), _p(rmax), _p(rinst), _p(errJ)))
     return {"rx": rx, "rl": rl, "rmax": rmax, "rinst": rinst, "errJ": errJ}
-
-
-def _refine_mesh(mesh, rmax):
-    """One node in the middle of the intervals with 1 < rmax < 32, two at the thirds of those with rmax >= 32 (a NaN counts as
-    such): the local error of an RK4 step falls by 32 when the step is halved.  Returns the new mesh; nodes are only added."""
-    mesh, r = np.asarray(mesh, dtype=np.float64), np.asarray(rmax, dtype=np.float64)
-    r = np.where(np.isnan(r), np.inf, r)
-    i1, = np.nonzero((r > 1) & (r < 32))
-    i2, = np.nonzero(r >= 32)
-    return np.sort(np.hstack((mesh, 0.5 * (mesh[i1] + mesh[i1 + 1]), (2 * mesh[i2] + mesh[i2 + 1]) / 3,
-                              (mesh[i2] + 2 * mesh[i2 + 1]) / 3)))
 
 
 def _pchip_batch(pts, u, tq):
@@ -249,41 +232,31 @@ def fb_sweep_adaptive_batch(prob, x0, tspan, options=None):
     if mesh.size < 2 or np.any(np.diff(mesh) <= 0):
         raise ValueError("fb_sweep_adaptive_batch: need an increasing InitMesh")
     o, options = _options(options)
-    x0 = _f(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
-    if x0.shape[0] != prob.nS:
-        x0 = _f(x0.reshape(prob.nS, -1))
+    x0 = x0_batch(prob, x0)
     batch = x0.shape[1]
     errorPts = matlab_linspace(mesh[0], mesh[-1], o.nERROR_PTS)
     lb = prob.batch_bounds[0] if prob.batch_bounds is not None else np.repeat(prob.ControlBounds[:, 0:1], batch, axis=1)
     u0g = u0e = None
-    meshes = []
-    while True:
-        integ = RK4Integrator(mesh)
+
+    def solve_round(mesh, integ):
+        nonlocal u0g, u0e
         if u0g is None and "u0" in options:
             u0g, u0e = _sample_u0(options.pop("u0"), prob, [integ.t, errorPts], batch)
         res = _sweep(prob, x0, integ, o, u0g, u0e)
-        meshes.append(int(mesh.size))
         conv = res["sweeps"] > 0
         ugrid = _pchip_batch(res["interpPts"], res["u"], integ.t)
         x, lam, J = compute_x_lam_J(prob, x0, mesh, ugrid, integrator=integ)
         est = x_lam_error(prob, mesh, ugrid, x, lam, rtol, atol, use=conv, integrator=integ)
-        if not conv.any():
-            status = 2
-            break
-        new = _refine_mesh(mesh, est["rmax"])
-        if new.size == mesh.size:
-            status = 0
-            break
-        if new.size > max_nodes:
-            status = 1
-            break
-        t2 = np.zeros(2 * new.size - 1)          # the 2N+1 grid of the next integrator (RK4Integrator.m:16-25)
-        t2[0::2], t2[1::2] = new, (new[:-1] + new[1:]) / 2
-        u0g, u0e = _pchip_batch(res["interpPts"], res["u"], t2), _pchip_batch(res["interpPts"], res["u"], errorPts)
-        for arr in (u0g, u0e):
-            arr[:, :, ~conv] = lb[:, None, ~conv]
-        del integ
-        mesh = new
-    res.update(x=x, lam=lam, J=J, ugrid=ugrid, mesh=res["tspan"], rx=est["rx"], rl=est["rl"], errJ=est["errJ"],
-               err_ok=conv & (est["rinst"] <= 1), meshes=meshes, mesh_status=status)
-    return res
+        res.update(x=x, lam=lam, J=J, ugrid=ugrid, mesh=res["tspan"], rx=est["rx"], rl=est["rl"], errJ=est["errJ"],
+                   err_ok=conv & (est["rinst"] <= 1))
+
+        def restart(new):
+            nonlocal u0g, u0e
+            t2 = np.zeros(2 * new.size - 1)          # the 2N+1 grid of the next integrator (RK4Integrator.m:16-25)
+            t2[0::2], t2[1::2] = new, (new[:-1] + new[1:]) / 2
+            u0g, u0e = _pchip_batch(res["interpPts"], res["u"], t2), _pchip_batch(res["interpPts"], res["u"], errorPts)
+            for arr in (u0g, u0e):
+                arr[:, :, ~conv] = lb[:, None, ~conv]
+        return res, conv, est["rmax"], restart
+
+    return adapt_mesh(mesh, max_nodes, 1, 32, solve_round)

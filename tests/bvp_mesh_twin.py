@@ -87,13 +87,14 @@ def rms(osys, tspan, y, dtype=np.float64):
     return np.sqrt(dtype(0.5) * (dtype(32) / dtype(45) * rm + dtype(49) / dtype(90) * rpm))
 
 
-def refine(tspan, rmsmax, tol):
-    """One node in the middle of the intervals with tol < rmsmax < 100 tol, two at the thirds of those with rmsmax >= 100 tol
-    (solve_bvp's rule and its modify_mesh); a NaN counts as >= 100 tol."""
-    x, r = np.asarray(tspan, dtype=np.float64), np.asarray(rmsmax, dtype=np.float64)
+def refine(mesh, r, lo, hi):
+    """One node in the middle of the intervals with lo < r < hi, two at the thirds of those with r >= hi; a NaN counts as the
+    latter.  (tol, 100 tol) on the rms residuals: solve_bvp's rule and its modify_mesh; (1, 32) on the ratios of
+    tests/xlam_err_twin.py."""
+    x, r = np.asarray(mesh, dtype=np.float64), np.asarray(r, dtype=np.float64)
     r = np.where(np.isnan(r), np.inf, r)
-    one = [i for i in range(r.size) if tol < r[i] < 100 * tol]
-    two = [i for i in range(r.size) if r[i] >= 100 * tol]
+    one = [i for i in range(r.size) if lo < r[i] < hi]
+    two = [i for i in range(r.size) if r[i] >= hi]
     new = list(x) + [0.5 * (x[i] + x[i + 1]) for i in one] + [(2 * x[i] + x[i + 1]) / 3 for i in two] + \
         [(x[i] + 2 * x[i + 1]) / 3 for i in two]
     return np.array(sorted(new))
@@ -145,7 +146,7 @@ def solve_adaptive(cases, oracle, mesh, tol, max_nodes=1000, **options):
         if not conv.any():
             status = 2
             break
-        new = refine(mesh, rmsmax, tol)
+        new = refine(mesh, rmsmax, tol, 100 * tol)
         if new.size == mesh.size:
             status = 0
             break

@@ -68,8 +68,8 @@ def test_refine_is_scipys_modify_mesh():
         i1, = np.nonzero((r > tol) & (r < 100 * tol))
         i2, = np.nonzero(r >= 100 * tol)
         want = modify_mesh(x, i1, i2)
-        assert np.array_equal(mt.refine(x, r, tol), want)
-    assert mt.refine([0.0, 1.0, 2.0], [np.nan, 0.0], 1.0).size == 5
+        assert np.array_equal(mt.refine(x, r, tol, 100 * tol), want)
+    assert mt.refine([0.0, 1.0, 2.0], [np.nan, 0.0], 1.0, 100.0).size == 5
 
 
 @pytest.mark.parametrize("name,m,x0", PROBLEMS, ids=[p[0] for p in PROBLEMS])
@@ -128,7 +128,7 @@ def test_cases_show_what_they_are_there_for(oracle):
     assert mc.UNION.cases[1].x0 == bc.NOT_CONVERGING.x0
     differs = False
     for r in un["rounds"][:-1]:
-        both = mt.refine(r["mesh"], r["rmsmax"], mc.UNION.tol)
-        own = [mt.refine(r["mesh"], r["rms"][:, b], mc.UNION.tol) for b in np.nonzero(r["converged"])[0]]
+        both = mt.refine(r["mesh"], r["rmsmax"], mc.UNION.tol, 100 * mc.UNION.tol)
+        own = [mt.refine(r["mesh"], r["rms"][:, b], mc.UNION.tol, 100 * mc.UNION.tol) for b in np.nonzero(r["converged"])[0]]
         differs = differs or (len(own) >= 2 and all(not np.array_equal(o, both) for o in own))
     assert differs

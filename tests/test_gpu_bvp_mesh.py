@@ -103,7 +103,7 @@ def test_rms_of_a_plugin_is_the_registry_problems(ocs, oracle):
         ring = [inst[b % len(inst)][1] for b in range(batch)]
         y = np.stack(ring, axis=2)
         got = {name: ocs.bvp_residuals(p, ts, y)["rms"] for name, p in (("plugin", pu), ("registry", reg))}
-        new = mt.refine(ts, np.array([2.0, 200.0] * len(ts))[:len(ts) - 1], 1.0)
+        new = mt.refine(ts, np.array([2.0, 200.0] * len(ts))[:len(ts) - 1], 1.0, 100.0)
         pro = {name: ocs.bvp_prolong(p, ts, y, new) for name, p in (("plugin", pu), ("registry", reg))}
         for b in range(min(batch, len(inst))):
             for what, twin, dev in (("rms", lambda d: mt.rms(osys, ts, ring[b], d), {k: v[:, b] for k, v in got.items()}),
@@ -117,23 +117,22 @@ def test_rms_of_a_plugin_is_the_registry_problems(ocs, oracle):
               f"prolong {np.array_equal(pro['plugin'], pro['registry'])}")
 
 
-def test_reductions(ocs, oracle):
-    """rmsmax / rmsinst are NumPy's maxima of the device's own rms; `use` masks instances out of rmsmax only; a NaN instance
-    shows as inf in its own rmsinst and, where in use, in rmsmax -- not in its neighbours' rmsinst; the same call twice gives
-    the same bits."""
-    ts, batch = bc.NONUNIFORM, 130
-    res, y, pr = check_rms(ocs, oracle, "bl3", ts, batch)
+def check_reductions(ocs, pr, ts, y, use, bad, at):
+    """rmsmax / rmsinst are NumPy's maxima of the device's own rms; `use` masks instances out of rmsmax only; a NaN in
+    instance `bad` at node `at` shows as inf in its own rmsinst and, where in use, in rmsmax -- not in its neighbours'
+    rmsinst; the same call twice gives the same bits."""
+    batch = y.shape[2]
+    res = ocs.bvp_residuals(pr, ts, y)
+    assert np.array_equal(res["rmsmax"], res["rms"].max(axis=1)) and np.array_equal(res["rmsinst"], res["rms"].max(axis=0))
     again = ocs.bvp_residuals(pr, ts, y)
     for k in ("rms", "rmsmax", "rmsinst"):
         assert np.array_equal(res[k], again[k]), k
-    use = np.arange(batch) % 4 == 1                         # (the ring has four members: one converged iterate alone)
     masked = ocs.bvp_residuals(pr, ts, y, use=use)
     assert np.array_equal(masked["rms"], res["rms"]) and np.array_equal(masked["rmsinst"], res["rmsinst"])
     assert np.array_equal(masked["rmsmax"], res["rms"][:, use].max(axis=1))
     assert not np.array_equal(masked["rmsmax"], res["rmsmax"])
     none = ocs.bvp_residuals(pr, ts, y, use=np.zeros(batch))
     assert (none["rmsmax"] == 0).all() and np.array_equal(none["rmsinst"], res["rmsinst"])
-    bad, at = 70, 20                                         # node 20: intervals 19 and 20 (chunk 2)
     yn = y.copy()
     yn[1, at, bad] = np.nan
     nan = ocs.bvp_residuals(pr, ts, yn)
@@ -145,6 +144,24 @@ def test_reductions(ocs, oracle):
     assert np.array_equal(nan["rmsmax"], want)
     out = ocs.bvp_residuals(pr, ts, yn, use=others)
     assert np.array_equal(out["rmsmax"], res["rms"][:, others].max(axis=1)) and out["rmsinst"][bad] == np.inf
+
+
+def test_reductions(ocs, oracle):
+    """batch 130 on the non-uniform grid; the mask keeps one member of the ring of four, a converged iterate alone; the NaN at
+    node 20: intervals 19 and 20 (chunk 2)"""
+    ts, batch = bc.NONUNIFORM, 130
+    _, y, pr = check_rms(ocs, oracle, "bl3", ts, batch)
+    check_reductions(ocs, pr, ts, y, np.arange(batch) % 4 == 1, 70, 20)
+
+
+def test_reductions_past_one_stride(ocs, oracle):
+    """batch 321 = 256 + 64 + 1, N 9: the row loop's second stride and the second workgroup of the per-instance half with its
+    partly filled last wave; two chunks, the second a one-interval tail.  The NaN in instance 300 (second stride) at node 8:
+    intervals 7 and 8, one in either chunk.  (Every instance is scaled on its own: the ring alone has four different rms.)"""
+    ts, batch = bc.EDGE_GRID[:10], 321
+    _, y, pr = check_rms(ocs, oracle, "bl3", ts, batch)
+    y = y * (1 + 0.01 * np.cos(np.arange(batch)))[None, None, :]
+    check_reductions(ocs, pr, ts, y, np.arange(batch) % 3 == 1, 300, 8)
 
 
 @pytest.mark.parametrize("kind", ["bl3", "logistic2", "logistic4", "per-trajectory"])
@@ -159,7 +176,7 @@ def test_prolong(ocs, oracle, kind):
         n = len(ts) - 1
         for name, r in (("one", np.full(n, 2.0)), ("two", np.full(n, 200.0)), ("mixed", np.array([0.1, 2.0, 200.0] * n)[:n]),
                         ("none", np.zeros(n))):
-            new = mt.refine(ts, r, 1.0)
+            new = mt.refine(ts, r, 1.0, 100.0)
             old = np.isin(new, ts)
             assert old.sum() == n + 1 and new.size == n + 1 + int((r == 2.0).sum()) + 2 * int((r == 200.0).sum())
             got = ocs.bvp_prolong(pr, ts, y, new)
@@ -259,7 +276,7 @@ def test_single_instances_against_solve_bvp(ocs, oracle, case):
 def test_host_helpers_are_the_twins(ocs):
     """the package's statement of the refinement rule and of the prolongation map against the twin's (which
     tests/test_bvp_mesh_twin.py holds against scipy's modify_mesh)"""
-    from ocs_amd import solvers
+    from ocs_amd import mesh
     rng = np.random.default_rng(5)
     for _ in range(100):
         n = int(rng.integers(1, 40))
@@ -269,9 +286,9 @@ def test_host_helpers_are_the_twins(ocs):
         r[rng.uniform(size=n) < 0.1] = tol
         r[rng.uniform(size=n) < 0.1] = 100 * tol
         r[rng.uniform(size=n) < 0.05] = np.nan
-        new = mt.refine(x, r, tol)
-        assert np.array_equal(solvers._refine_mesh(x, r, tol), new)
-        idx, theta = solvers._prolong_map(x, new)
+        new = mt.refine(x, r, tol, 100 * tol)
+        assert np.array_equal(mesh.refine_mesh(x, r, tol, 100 * tol), new)
+        idx, theta = mesh._prolong_map(x, new)
         ti, tt = mt.locate(x, new)
         assert np.array_equal(idx, ti) and np.array_equal(theta, tt) and theta[-1] == 1.0 and (theta[np.isin(new, x)][:-1] == 0.0).all()
 
@@ -285,7 +302,7 @@ def test_solver_is_untouched_by_the_mesh_calls(ocs, oracle):
     gi = ocs.RK4Integrator(bc.NONUNIFORM)
     before = ocs.bvp_solver_batch(pr, X0, bc.NONUNIFORM, {"nINTERP_PTS": 41}, integrator=gi)
     ocs.bvp_residuals(pr, bc.NONUNIFORM, before["y"], integrator=gi)
-    ocs.bvp_prolong(pr, bc.NONUNIFORM, before["y"], mt.refine(bc.NONUNIFORM, np.full(37, 2.0), 1.0), integrator=gi)
+    ocs.bvp_prolong(pr, bc.NONUNIFORM, before["y"], mt.refine(bc.NONUNIFORM, np.full(37, 2.0), 1.0, 100.0), integrator=gi)
     after = ocs.bvp_solver_batch(pr, X0, bc.NONUNIFORM, {"nINTERP_PTS": 41}, integrator=gi)
     for k in ("y", "x", "lam", "u", "J", "iterations", "converged", "resnorm"):
         assert np.array_equal(before[k], after[k]), k

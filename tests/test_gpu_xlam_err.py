@@ -120,13 +120,9 @@ def test_plugin(ocs):
         check(ocs, f"plugin N {N} batch {batch}", dev, twin, ts, x0, ug)
 
 
-def test_reductions_masks_nan_and_bits(ocs):
-    """`use` masks rmax but not rinst; a NaN planted in one instance's x gives inf in its rinst and, where it is in use, in
-    rmax, and leaves every other instance's numbers bit-identical; two calls give equal bits; _dev and host agree bit for bit"""
-    import torch
-    from ocs_amd import _lib
-    from ocs_amd.integrator import _dptr
-    batch, ts = 69, grid_of(13)
+def check_reductions(ocs, batch, ts, bad, at):
+    """`use` masks rmax but not rinst; a NaN planted in x of instance `bad` at node `at` gives inf in its rinst and, where it is in
+    use, in rmax, and leaves every other instance's numbers bit-identical; two calls give equal bits"""
     N = ts.size - 1
     dev = ocs.LogisticProblem(M[:2], 1.5, 0.05, BOUNDS)
     x0, ug = inputs(2, 1, ts, batch)
@@ -141,7 +137,6 @@ def test_reductions_masks_nan_and_bits(ocs):
     assert not np.array_equal(masked["rmax"], res["rmax"])
     none = ocs.x_lam_error(dev, ts, ug, x, lam, RTOL, ATOL, use=np.zeros(batch))
     assert (none["rmax"] == 0).all() and np.array_equal(none["rinst"], res["rinst"])
-    bad, at = 66, 9                                        # node 9: intervals 8 and 9 (chunk 1), instance in the wave tail
     xn = x.copy()
     xn[1, at, bad] = np.nan
     nan = ocs.x_lam_error(dev, ts, ug, xn, lam, RTOL, ATOL)
@@ -156,6 +151,25 @@ def test_reductions_masks_nan_and_bits(ocs):
     assert np.array_equal(nan["rmax"][keep], res["rmax"][keep])
     out = ocs.x_lam_error(dev, ts, ug, xn, lam, RTOL, ATOL, use=others)
     assert np.array_equal(out["rmax"], xt.reductions(res["rx"], res["rl"], others)[0]) and out["rinst"][bad] == np.inf
+    return dev, ug, x, lam, res
+
+
+def test_reductions_past_one_stride(ocs):
+    """batch 321 = 256 + 64 + 1, N 9: the row loop's second stride and the second workgroup of the per-instance half with its
+    partly filled last wave; two chunks, the second a one-interval tail.  The NaN in instance 300 (second stride) at node 8:
+    intervals 7 and 8, one in either chunk."""
+    check_reductions(ocs, 321, grid_of(9), 300, 8)
+
+
+def test_reductions_masks_nan_and_bits(ocs):
+    """batch 69, N 13; the NaN at node 9: intervals 8 and 9 (chunk 1), instance in the wave tail; then: _dev and host agree bit
+    for bit"""
+    import torch
+    from ocs_amd import _lib
+    from ocs_amd.integrator import _dptr
+    batch, ts = 69, grid_of(13)
+    N = ts.size - 1
+    dev, ug, x, lam, res = check_reductions(ocs, batch, ts, 66, 9)
     # the device entry point on the arrays of ocs_compute_x_lam_dev's shapes (x with the cost row, ldx = nS + 1)
     gi = ocs.RK4Integrator(ts)
     cu = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device="cuda")

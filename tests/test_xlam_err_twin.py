@@ -98,13 +98,13 @@ def test_the_coupling_error_is_seen():
 def test_refinement_rule():
     mesh = np.array([0.0, 1.0, 2.5, 3.0, 4.0, 6.0, 7.0])
     r = np.array([0.5, 1.0, 1.0000001, 31.999, 32.0, np.nan])
-    new = xt.refine(mesh, r)
+    new = xt.refine(mesh, r, 1, 32)
     want = sorted(list(mesh) + [0.5 * (2.5 + 3.0), 0.5 * (3.0 + 4.0), (2 * 4.0 + 6.0) / 3, (4.0 + 2 * 6.0) / 3, (2 * 6.0 + 7.0) / 3,
                                 (6.0 + 2 * 7.0) / 3])
     assert np.array_equal(new, np.array(want))
     assert np.isin(mesh, new).all() and np.all(np.diff(new) > 0)
-    assert np.array_equal(xt.refine(mesh, np.zeros(6)), mesh) and np.array_equal(xt.refine(mesh, np.ones(6)), mesh)
-    assert xt.refine(mesh, np.full(6, np.inf)).size == mesh.size + 12
+    assert np.array_equal(xt.refine(mesh, np.zeros(6), 1, 32), mesh) and np.array_equal(xt.refine(mesh, np.ones(6), 1, 32), mesh)
+    assert xt.refine(mesh, np.full(6, np.inf), 1, 32).size == mesh.size + 12
     rmax, rinst = xt.reductions(np.array([[1.0, np.nan], [3.0, 0.1]]), np.array([[2.0, 0.0], [0.5, 0.2]]), use=[1, 0])
     assert np.array_equal(rmax, [2.0, 3.0]) and np.array_equal(rinst, [3.0, np.inf])
     rmax, _ = xt.reductions(np.array([[1.0, np.nan]]), np.array([[2.0, 0.0]]), use=[0, 0])
@@ -162,7 +162,7 @@ def test_new_symbols_are_exported_and_refuse_null_handles(pkg):
 
 
 def test_package_refinement_rule_is_the_twins(pkg):
-    from ocs_amd import sweep
+    from ocs_amd import mesh
     rng = np.random.default_rng(5)
     for _ in range(100):
         n = int(rng.integers(1, 40))
@@ -171,4 +171,4 @@ def test_package_refinement_rule_is_the_twins(pkg):
         r[rng.uniform(size=n) < 0.1] = 1.0
         r[rng.uniform(size=n) < 0.1] = 32.0
         r[rng.uniform(size=n) < 0.05] = np.nan
-        assert np.array_equal(sweep._refine_mesh(x, r), xt.refine(x, r))
+        assert np.array_equal(mesh.refine_mesh(x, r, 1, 32), xt.refine(x, r, 1, 32))

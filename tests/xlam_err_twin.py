@@ -16,6 +16,7 @@ import numpy as np
 
 from tests import fbs_twin as ft
 from tests import rk4_twin as tw
+from tests.bvp_mesh_twin import refine
 
 L = tw.L
 CHUNK = 8            # intervals per partial sum of errJ (kErrChunk)
@@ -187,18 +188,6 @@ def reductions(rx, rl, use=None):
     return rmax, np.max(r, axis=0)
 
 
-def refine(mesh, rmax):
-    """One node in the middle of the intervals with 1 < rmax < 32, two at the thirds of those with rmax >= 32; a NaN counts
-    as the latter."""
-    x, r = np.asarray(mesh, dtype=np.float64), np.asarray(rmax, dtype=np.float64)
-    r = np.where(np.isnan(r), np.inf, r)
-    one = [i for i in range(r.size) if 1 < r[i] < 32]
-    two = [i for i in range(r.size) if r[i] >= 32]
-    new = list(x) + [0.5 * (x[i] + x[i + 1]) for i in one] + [(2 * x[i] + x[i + 1]) / 3 for i in two] + \
-        [(x[i] + 2 * x[i + 1]) / 3 for i in two]
-    return np.array(sorted(new))
-
-
 def solve_adaptive(oracle, oprobs, tprobs, x0, mesh, rtol, atol, options, max_nodes=20000):
     """The loop of fb_sweep_adaptive_batch with the oracle's fb_sweep as the sweep: oprobs / tprobs the oracle's and the twin's
     problem of every instance, x0 [nS][B].  Returns a dict: mesh, mesh_status, meshes, sweeps [B], x, lam [nS][N+1][B], J,
@@ -234,7 +223,7 @@ def solve_adaptive(oracle, oprobs, tprobs, x0, mesh, rtol, atol, options, max_no
         if not conv.any():
             status = 2
             break
-        new = refine(mesh, rmax)
+        new = refine(mesh, rmax, 1, 32)
         if new.size == mesh.size:
             status = 0
             break
